@@ -17,7 +17,12 @@ scaling): every rank holds a key shard (wires and Z positions) and gathers its
 cyclic slices of A/B/C, computeH runs as a four-step distributed NTT with three
 RCCL all-to-alls, and the 576-B partials are all-gathered and combined.
 
-Also reported: the G1 MSM throughput inside the prove and a standalone 2^20 G1
+A plain run sets the key up, warms up, times --steps proofs and prints the
+headline line (--dump-outputs DIR also writes the last timed proof).  The
+host-memory prove in "other_inputs" and everything below are measured only
+with --full.
+
+With --full also reported: the G1 MSM throughput inside the prove and a standalone 2^20 G1
 MSM (configs[1]), the 2^24 Fr NTT round trip (configs[2]), the BLS12-381 PlonK
 hot ops and prove (configs[4]), and the C restatement (oracle/) of the same
 prove timed on the host cores as cpu_baseline.
@@ -99,7 +104,19 @@ def mimc_shape(log_n):
     return dict(chains=chains, ncons=ncons, nw=nw, nb_public=2, infA=infA, infB=infB)
 
 
-def main():
+def dump_outputs(directory, proof):
+    """--dump-outputs: the proof the last timed step returned, one file per point
+    (Ar 64 B, Bs 128 B, Krs 64 B: affine coordinates, Montgomery bytes), each byte
+    a float64.  The key, the solution and r, s are seeded, so two builds that
+    compute the same proof write identical files."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name in ("Ar", "Bs", "Krs"):
+        a = np.frombuffer(getattr(proof, name), dtype=np.uint8).astype(np.float64)
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -113,6 +130,13 @@ def main():
                     help="BLS12-381 PlonK measurement size, BASELINE configs[4] (0 = skip)")
     ap.add_argument("--host-inputs", action="store_true",
                     help="headline from host memory (H2D inside the step) instead of HBM-resident inputs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything else this file knows: the other input "
+                         "placement, the kernel roofline, the prove variants, the GPU solver, the N-GPU "
+                         "projections, the standalone MSM / NTT, PlonK and the CPU baseline (a plain run "
+                         "times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the proof's Ar, Bs, Krs) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--solver", type=int, default=1,
                     help="time the GPU R1CS solver on the headline circuit and witness -> proof (1/0)")
@@ -137,9 +161,12 @@ def main():
     ap.add_argument("--devices", default=None,
                     help="one-process path: comma-separated GPU id per key shard (default 0..N-1); ids may "
                          "repeat to rehearse N shards on fewer GPUs (n_gpus = distinct ids)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
 
-    rank = int(os.environ.get("RANK", "0"))
+
+def main():
+    args = parse_args()
+    rank =int(os.environ.get("RANK", "0"))
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if env_world > 1 or args.launcher == "torch":
@@ -258,8 +285,10 @@ def main():
     ncons = g.shape["ncons"]
     value = ncons * args.steps / el  # constraints/s of the whole job (one proof per step)
     same = g.proof_identical_on_all_ranks()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, g.last)
     other = None
-    if world == 1:  # the other input placement, same key, same step count (also N GPUs in one process)
+    if args.full and world == 1:  # the other input placement, same key, same step count (also N GPUs in one process)
         g.sol = g.sol_dev if args.host_inputs else g.sol_host
         o_el, o_steps, o_slow, o_stage = timed_proves(args.steps, 1)
         other = {"inputs": "device" if args.host_inputs else "host",
@@ -268,38 +297,6 @@ def main():
                  "note": "host: W, A, B, C in host memory, uploaded through pinned staging inside the step "
                          "(PCIe-inclusive, the span of icicle.go:231-278); device: already in HBM"}
         g.sol = g.sol_host if args.host_inputs else g.sol_dev
-
-    # ---- roofline of the dominant kernel: HIP events on its launch stream, over
-    # ROOFLINE_PROVES proves with the five tasks run one after another
-    # (GG_G16_SERIAL=1), so an event pair brackets the kernel alone -- with five
-    # busy streams it would also count the wait for CUs held by the other MSMs.
-    # These are the last k_accum_range<Fp2> launches of the run; the committed
-    # rocprof summary reports the average of exactly those dispatches
-    # (tools/prof_summary.py --last).
-    _lib.profile_enable(True)
-    os.environ["GG_G16_SERIAL"] = "1"
-    try:
-        for _ in range(ROOFLINE_PROVES):
-            g.prove()
-    finally:
-        del os.environ["GG_G16_SERIAL"]
-    kernels = {}
-    for name in ("msm_sort", "msm_accum", "msm_accum_g2", "msm_accum2", "msm_reduce", "ntt_pass"):
-        tot, cnt, units = _lib.profile_get(name)
-        kernels[name] = {"avg_ms": tot / cnt if cnt else None, "launches_per_proof": cnt / ROOFLINE_PROVES,
-                         "total_ms_per_proof": tot / ROOFLINE_PROVES, "units_per_launch": units / cnt if cnt else None}
-    _lib.profile_enable(False)
-    wl = {"workload": "groth16", "log_n": args.log_n, "n_gpus": n_shards}
-    # dominant kernel per proof: the G1 bucket accumulation (4 launches: A, B1, K, Z);
-    # the G2 accumulation (the longest single launch) is the second entry
-    r_g1 = accum_roofline(kernels["msm_accum"], 64, "k_accum_range<gg::Fe<gg::FpCfg>, ", wl,
-                          "k_accum_range<Fe<FpCfg>> (BN254 G1 bucket accumulation, radix-2^29 XYZZ mixed adds: "
-                          "the A, B1, K and Z MSMs -- the largest share of each proof)", g.g1_windows)
-    r_g2 = accum_roofline(kernels["msm_accum_g2"], 128, "k_accum_range<gg::Fp2, ", wl,
-                          "k_accum_range<Fp2> (BN254 G2 bucket accumulation of the B MSM: the longest single "
-                          "launch of the prove)", g.g2_windows)
-    roofline = dict(r_g1)
-    roofline["others"] = [r_g2]
 
     out = {
         "metric": METRIC, "value": value, "unit": "constraints/s", "n_gpus": n_gpus,
@@ -333,6 +330,55 @@ def main():
                    "split": g.split,
                    "launcher": mode, "shards": n_shards},
         "prove_ms": ms_per_step, "stage_ms": stage, "proof_identical_on_all_ranks": same,
+    }
+    if mode == "mpk":  # where each shard's time went (last timed proof): compute vs barrier waits vs xGMI
+        out["shard_timings"] = g.shard_timings
+        out["peer_access"] = g.pk.peer_access()
+    elif mode == "torch":
+        out["shard_timings"] = g.rank_timings(dist, xdev)
+
+    if not args.full:  # a plain run: the headline only
+        g.close()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- roofline of the dominant kernel: HIP events on its launch stream, over
+    # ROOFLINE_PROVES proves with the five tasks run one after another
+    # (GG_G16_SERIAL=1), so an event pair brackets the kernel alone -- with five
+    # busy streams it would also count the wait for CUs held by the other MSMs.
+    # These are the last k_accum_range<Fp2> launches of the run; the committed
+    # rocprof summary reports the average of exactly those dispatches
+    # (tools/prof_summary.py --last).
+    _lib.profile_enable(True)
+    os.environ["GG_G16_SERIAL"] = "1"
+    try:
+        for _ in range(ROOFLINE_PROVES):
+            g.prove()
+    finally:
+        del os.environ["GG_G16_SERIAL"]
+    kernels = {}
+    for name in ("msm_sort", "msm_accum", "msm_accum_g2", "msm_accum2", "msm_reduce", "ntt_pass"):
+        tot, cnt, units = _lib.profile_get(name)
+        kernels[name] = {"avg_ms": tot / cnt if cnt else None, "launches_per_proof": cnt / ROOFLINE_PROVES,
+                         "total_ms_per_proof": tot / ROOFLINE_PROVES, "units_per_launch": units / cnt if cnt else None}
+    _lib.profile_enable(False)
+    wl = {"workload": "groth16", "log_n": args.log_n, "n_gpus": n_shards}
+    # dominant kernel per proof: the G1 bucket accumulation (4 launches: A, B1, K, Z);
+    # the G2 accumulation (the longest single launch) is the second entry
+    r_g1 = accum_roofline(kernels["msm_accum"], 64, "k_accum_range<gg::Fe<gg::FpCfg>, ", wl,
+                          "k_accum_range<Fe<FpCfg>> (BN254 G1 bucket accumulation, radix-2^29 XYZZ mixed adds: "
+                          "the A, B1, K and Z MSMs -- the largest share of each proof)", g.g1_windows)
+    r_g2 = accum_roofline(kernels["msm_accum_g2"], 128, "k_accum_range<gg::Fp2, ", wl,
+                          "k_accum_range<Fp2> (BN254 G2 bucket accumulation of the B MSM: the longest single "
+                          "launch of the prove)", g.g2_windows)
+    roofline = dict(r_g1)
+    roofline["others"] = [r_g2]
+
+    out.update({
         "other_inputs": other,
         "product_paths": {
             "value": "solution resident in HBM: the drop-in's path for hint-free circuits, whose R1CS the "
@@ -343,11 +389,8 @@ def main():
             "solver.witness_to_proof_ms": "witness (host, 2 MB) -> GPU solve -> proof from HBM: the end-to-end "
                                           "time of the hint-free path"},
         "roofline": roofline, "kernels": kernels,
-    }
-    if mode == "mpk":  # where each shard's time went (last timed proof): compute vs barrier waits vs xGMI
-        out["shard_timings"] = g.shard_timings
-        out["peer_access"] = g.pk.peer_access()
-    elif mode == "torch":
+    })
+    if mode == "torch":  # --full gathers them here, after the roofline's proves, as it always has
         out["shard_timings"] = g.rank_timings(dist, xdev)
 
     # watchdog over the extras: the headline is already measured

@@ -134,6 +134,34 @@ def test_bench_reports_planned_exchange_and_devices():
     assert "1/%d slice per GPU" not in src
 
 
+def test_bench_dump_outputs_round_trips(tmp_path):
+    """bench.py --dump-outputs: one float64 .npy per proof point, each byte kept
+    exactly (no GPU needed: the writer only takes a Proof)."""
+    import numpy as np
+    import bench
+    from helpers import golden
+    from gnark_amd import groth16
+    g = golden()["groth16"][0]
+    pr = groth16.Proof(b(g["Ar"]), b(g["Bs"]), b(g["Krs"]))
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), pr)
+    assert sorted(p.name for p in out.iterdir()) == ["Ar.npy", "Bs.npy", "Krs.npy"]
+    for name, size in (("Ar", 64), ("Bs", 128), ("Krs", 64)):
+        a = np.load(out / (name + ".npy"))
+        assert a.dtype == np.float64 and a.shape == (size,)
+        assert a.astype(np.uint8).tobytes() == getattr(pr, name)
+
+
+def test_bench_plain_run_is_the_headline_only():
+    """bench.py: the extra measurements sit behind --full (off by default), and
+    --dump-outputs takes a directory."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 3, 1)
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
 def test_every_environment_knob_is_documented():
     """Every GG_* variable the library reads is in INTEGRATION.md's tables."""
     csrc = os.path.join(ROOT, "gnark-fork_amd", "csrc")
