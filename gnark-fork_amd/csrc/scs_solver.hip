@@ -3,8 +3,9 @@
 // Mul/Add forms it generalises) run level by level as in solver.go:418-533,
 // then evaluateLROSmallDomain (constraint/bls12-381/system.go:221-264) builds
 // the L, R, O columns the PlonK prover takes (gg_plonk_prove, inputs on
-// device).  Hint-free systems; BLS12-381 fr (PlonK, BASELINE configs[4]) and
-// BN254 fr.
+// device).  BLS12-381 fr (PlonK, BASELINE configs[4]) and BN254 fr.  Hint
+// calls: gnark's own seven hints run on the GPU too (gg_scs_set_hints,
+// hints.cuh); a system with any other hint keeps gnark's host solver.
 //
 // Constraint c: qL xa + qR xb + qO xc + qM xa xb + qC = 0 with
 //   wires[3c + 0..2] = xa, xb, xc and qidx[5c + 0..4] = qL, qR, qO, qM, qC
@@ -19,6 +20,7 @@
 // A zero denominator is errDivideByZero.
 #include "common.h"
 #include "field.cuh"
+#include "hints.cuh"
 #include "strands.h"
 #include <algorithm>
 #include <cstdlib>
@@ -257,6 +259,9 @@ struct gg_scs {
     std::vector<uint32_t> sl_seg_off;
     DevBuf unk, order, seg_start;
     size_t n_super = 0, n_seg = 0;
+    HintSet hints;        // gg_scs_set_hints: a handle with hints runs the level schedule
+    uint32_t one_idx = 0xffffffffu;  // index of the coefficient 1 (hint inputs skip the product)
+    bool solved_once = false;
     hipStream_t st = nullptr;
     hipGraphExec_t graph = nullptr;
     std::mutex mu;
@@ -272,6 +277,13 @@ void invert_table(const void* coeffs, size_t n, std::vector<Fe<C>>& inv) {
     const Fe<C>* cf = (const Fe<C>*)coeffs;
     inv.resize(n);
     for (size_t i = 0; i < n; i++) inv[i] = cf[i].is_zero() ? Fe<C>::zero() : inverse(cf[i]);
+}
+template <class C>
+uint32_t find_one(const void* coeffs, size_t n) {
+    const Fe<C>* cf = (const Fe<C>*)coeffs;
+    for (size_t i = 0; i < n; i++)
+        if (cf[i] == Fe<C>::one()) return (uint32_t)i;
+    return 0xffffffffu;
 }
 
 template <class C>
@@ -292,6 +304,7 @@ void enqueue_scs_levels(gg_scs* h) {
     }
     const uint32_t* lc = h->level_cons.as<uint32_t>();
     for (size_t l = 0; l + 1 < h->level_off.size(); l++) {
+        h->hints.enqueue_level<C>(l, h->st, d.coef, h->one_idx, d.W, d.solved, d.fail);
         const uint32_t a = h->level_off[l], cnt = h->level_off[l + 1] - a;
         if (!cnt) continue;
         hipLaunchKernelGGL(k_scs_level<C>, dim3(grid_for(cnt, 256)), dim3(256), 0, h->st, d, lc + a, cnt);
@@ -331,7 +344,7 @@ void scs_solve_impl(gg_scs* h, const void* in, size_t n_in) {
     // schedule: strands when the levels allow it (GG_SOLVER_LEVELS=1: level launches)
     if (h->strand_nin != (long long)n_in) {
         const bool levels_only = getenv("GG_SOLVER_LEVELS") && atoi(getenv("GG_SOLVER_LEVELS"));
-        h->strands = !levels_only && build_scs_strands(h, n_in);
+        h->strands = !levels_only && !h->hints.any() && build_scs_strands(h, n_in);
         h->strand_nin = (long long)n_in;
         if (h->graph) {
             (void)hipGraphExecDestroy(h->graph);
@@ -407,6 +420,7 @@ extern "C" int gg_scs_create(int curve, size_t n_wires, size_t n_constraints, si
         h->nb_public = nb_public;
         h->dom = dom;
         h->ncoef = n_coeffs;
+        h->one_idx = curve == GG_CURVE_BN254 ? find_one<FrCfg>(coeffs, n_coeffs) : find_one<FrBlsCfg>(coeffs, n_coeffs);
         h->level_off.assign(level_off, level_off + n_levels + 1);
         h->h_wires.assign(wires, wires + 3 * n_constraints);
         h->h_level_cons.assign(level_cons, level_cons + n_constraints);
@@ -474,6 +488,9 @@ extern "C" int gg_scs_solve(gg_scs_t h, const void* witness, size_t n_witness, i
         throw Error(GG_ERR_INVALID_ARG, "invalid witness size, got " + std::to_string(n_witness) + ", expected " +
                                             std::to_string(h->expect_inputs));
     std::lock_guard<std::mutex> lk(h->mu);
+    GG_CHECK(!h->hints.any() || h->hints.min_out >= n_witness, GG_ERR_INVALID_ARG,
+             "a hint's output range touches a witness wire");
+    h->solved_once = true;
     GG_HIP(hipSetDevice(h->device));
     if (failed) *failed = -1;
     const void* in = witness;
@@ -493,6 +510,8 @@ extern "C" int gg_scs_solve(gg_scs_t h, const void* witness, size_t n_witness, i
     GG_HIP(hipMemcpyAsync(fail, h->fail.p, 12, hipMemcpyDeviceToHost, h->st));
     GG_HIP(hipMemcpyAsync(&unsolved, h->cnt.p, 8, hipMemcpyDeviceToHost, h->st));
     GG_WAIT_STREAM(h->st);
+    GG_CHECK(fail[1] == 0xffffffffu || !(fail[1] & HINT_FAIL_BIT) || !h->hints.any(), GG_ERR_INVALID_ARG,
+             hint_unsolved_message(fail[1]));
     GG_CHECK(fail[1] == 0xffffffffu, GG_ERR_INVALID_ARG,
              "constraint #" + std::to_string(fail[1]) +
                  ": more than one unsolved wire at its level (the levels do not match the system)");
@@ -532,9 +551,26 @@ extern "C" int gg_scs_schedule(gg_scs_t h, int* strands, size_t* launches, size_
         for (size_t l = 0; l < h->n_super; l++) nl += h->sl_seg_off[l + 1] > h->sl_seg_off[l];
     } else {
         for (size_t l = 0; l + 1 < h->level_off.size(); l++) nl += h->level_off[l + 1] > h->level_off[l];
+        nl += h->hints.launches();
     }
     if (strands) *strands = h->strands ? 1 : 0;
     if (launches) *launches = nl;
     if (segments) *segments = h->strands ? h->n_seg : 0;
+    GG_CAPI_END
+}
+
+extern "C" int gg_scs_set_hints(gg_scs_t h, size_t n_hints, const uint32_t* hint_id, const uint32_t* in_off,
+                                const uint32_t* expr_off, const uint32_t* term_wire, const uint32_t* term_coeff,
+                                const uint32_t* out_start, const uint32_t* out_end, const uint32_t* level_off,
+                                const uint32_t* level_hints, size_t n_levels) {
+    GG_CAPI_BEGIN
+    GG_CHECK(h, GG_ERR_INVALID_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    GG_CHECK(!h->solved_once, GG_ERR_INVALID_ARG, "set_hints: the handle has already solved");
+    GG_HIP(hipSetDevice(h->device));
+    // wires below the witness length are inputs (gg_scs_set_inputs, when called; no ONE_WIRE)
+    const size_t first_internal = h->expect_inputs >= 0 ? (size_t)h->expect_inputs : 0;
+    h->hints.init(h->nw, h->ncoef, h->ncons, first_internal, h->level_off.size() - 1, n_hints, hint_id, in_off,
+                  expr_off, term_wire, term_coeff, out_start, out_end, level_off, level_hints, n_levels);
     GG_CAPI_END
 }

@@ -1,6 +1,8 @@
 // R1CS solver on the GPU: constraint/bn254/solver.go:418-608
-// (run + solveR1C) for R1CS without hint calls, BN254 or BLS12-381 fr
-// (gg_r1cs_create_ex; constraint/bls12-381/solver.go is the same code).
+// (run + solveR1C), BN254 or BLS12-381 fr (gg_r1cs_create_ex;
+// constraint/bls12-381/solver.go is the same code).  Hint calls: gnark's own
+// seven hints run on the GPU too (gg_r1cs_set_hints, hints.cuh); a system with
+// any other hint keeps gnark's host solver.
 //
 // The system is handed over once in CSR form -- exactly what gnark's public
 // R1CS API yields (r1cs.GetR1Cs() terms, r1cs.Coefficients, r1cs.Levels):
@@ -21,6 +23,7 @@
 // launches per solve otherwise).
 #include "common.h"
 #include "field.cuh"
+#include "hints.cuh"
 #include "strands.h"
 #include <algorithm>
 #include <cstdlib>
@@ -268,6 +271,8 @@ struct gg_r1cs {
     std::vector<uint32_t> sl_seg_off;  // segments of super-level l: [sl_seg_off[l], sl_seg_off[l+1])
     DevBuf unk, order, seg_start;
     size_t n_super = 0, n_seg = 0;
+    HintSet hints;        // gg_r1cs_set_hints: a handle with hints runs the level schedule
+    bool solved_once = false;
     hipStream_t st = nullptr;
     hipGraphExec_t graph = nullptr;
     std::mutex mu;
@@ -439,6 +444,7 @@ static void enqueue_levels_t(gg_r1cs* r) {
     }
     const uint32_t* lc = r->level_cons.as<uint32_t>();
     for (size_t l = 0; l + 1 < r->level_off.size(); l++) {
+        r->hints.enqueue_level<FC>(l, r->st, d.coef, d.one_idx, d.W, d.solved, d.fail);
         const uint32_t a = r->level_off[l], cnt = r->level_off[l + 1] - a;
         if (!cnt) continue;
         hipLaunchKernelGGL(k_solve_level<FC>, dim3(grid_for(cnt, 256)), dim3(256), 0, r->st, d, lc + a, cnt);
@@ -472,6 +478,9 @@ extern "C" int gg_r1cs_solve(gg_r1cs_t r, const void* witness, size_t n_witness,
                                             std::to_string(r->expect_inputs));
     GG_CHECK(n_witness == 0 || witness, GG_ERR_INVALID_ARG, "null witness");
     std::lock_guard<std::mutex> lk(r->mu);
+    GG_CHECK(!r->hints.any() || r->hints.min_out > n_witness, GG_ERR_INVALID_ARG,
+             "a hint's output range touches a witness wire");
+    r->solved_once = true;
     GG_HIP(hipSetDevice(r->device));
     if (unsatisfied) *unsatisfied = -1;
     const void* in = witness;
@@ -491,7 +500,7 @@ extern "C" int gg_r1cs_solve(gg_r1cs_t r, const void* witness, size_t n_witness,
     // schedule: strands when the levels allow it (GG_SOLVER_LEVELS=1: level launches)
     if (r->strand_nin != (long long)n_witness) {
         const bool levels_only = getenv("GG_SOLVER_LEVELS") && atoi(getenv("GG_SOLVER_LEVELS"));
-        r->strands = !levels_only && build_strands(r, n_witness);
+        r->strands = !levels_only && !r->hints.any() && build_strands(r, n_witness);
         r->strand_nin = (long long)n_witness;
         if (r->graph) {
             (void)hipGraphExecDestroy(r->graph);
@@ -523,6 +532,8 @@ extern "C" int gg_r1cs_solve(gg_r1cs_t r, const void* witness, size_t n_witness,
     GG_HIP(hipMemcpyAsync(fail, r->fail.p, 8, hipMemcpyDeviceToHost, r->st));
     GG_HIP(hipMemcpyAsync(&unsolved, r->cnt.p, 8, hipMemcpyDeviceToHost, r->st));
     GG_WAIT_STREAM(r->st);
+    GG_CHECK(fail[1] == 0xffffffffu || !(fail[1] & HINT_FAIL_BIT) || !r->hints.any(), GG_ERR_INVALID_ARG,
+             hint_unsolved_message(fail[1]));
     GG_CHECK(fail[1] == 0xffffffffu, GG_ERR_INVALID_ARG,
              "constraint #" + std::to_string(fail[1]) +
                  ": more than one unsolved wire at its level, or a zero coefficient on the unknown "
@@ -562,9 +573,54 @@ extern "C" int gg_r1cs_schedule(gg_r1cs_t r, int* strands, size_t* launches, siz
         for (size_t l = 0; l < r->n_super; l++) nl += r->sl_seg_off[l + 1] > r->sl_seg_off[l];
     } else {
         for (size_t l = 0; l + 1 < r->level_off.size(); l++) nl += r->level_off[l + 1] > r->level_off[l];
+        nl += r->hints.launches();
     }
     if (strands) *strands = r->strands ? 1 : 0;
     if (launches) *launches = nl;
     if (segments) *segments = r->strands ? r->n_seg : 0;
+    GG_CAPI_END
+}
+
+// ---- gnark's built-in hints (hints.cuh) ------------------------------------
+
+extern "C" int gg_hint_supported(uint32_t hint_id, int* supported, const char** go_name) {
+    GG_CAPI_BEGIN
+    const int k = hint_kind_of(hint_id);
+    if (supported) *supported = k >= 0 ? 1 : 0;
+    if (go_name) *go_name = k >= 0 ? hint_table()[k].go_name : nullptr;
+    GG_CAPI_END
+}
+
+extern "C" int gg_hint_eval_host(int curve, uint32_t hint_id, const void* inputs, size_t n_in, void* outputs,
+                                 size_t n_out) {
+    GG_CAPI_BEGIN
+    GG_CHECK(curve == GG_CURVE_BN254 || curve == GG_CURVE_BLS12_381, GG_ERR_INVALID_ARG, "unknown curve");
+    const int k = hint_kind_of(hint_id);
+    GG_CHECK(k >= 0, GG_ERR_UNSUPPORTED,
+             "HintID " + hint_id_hex(hint_id) + " is not one of gnark's built-in hints the GPU solver evaluates");
+    const HintInfo& hi = hint_table()[k];
+    GG_CHECK((int)n_in == hi.n_in && n_in < 3, GG_ERR_INVALID_ARG,
+             std::string(hi.go_name) + " takes " + std::to_string(hi.n_in) + " input(s)");
+    GG_CHECK(hi.n_out < 0 || (int)n_out == hi.n_out, GG_ERR_INVALID_ARG,
+             std::string(hi.go_name) + " has " + std::to_string(hi.n_out) + " output(s)");
+    GG_CHECK(inputs && (outputs || !n_out), GG_ERR_INVALID_ARG, "null argument");
+    if (curve == GG_CURVE_BN254) hint_eval_host<FrCfg>((uint32_t)k, inputs, n_in, outputs, n_out);
+    else hint_eval_host<FrBlsCfg>((uint32_t)k, inputs, n_in, outputs, n_out);
+    GG_CAPI_END
+}
+
+extern "C" int gg_r1cs_set_hints(gg_r1cs_t r, size_t n_hints, const uint32_t* hint_id, const uint32_t* in_off,
+                                 const uint32_t* expr_off, const uint32_t* term_wire, const uint32_t* term_coeff,
+                                 const uint32_t* out_start, const uint32_t* out_end, const uint32_t* level_off,
+                                 const uint32_t* level_hints, size_t n_levels) {
+    GG_CAPI_BEGIN
+    GG_CHECK(r, GG_ERR_INVALID_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(r->mu);
+    GG_CHECK(!r->solved_once, GG_ERR_INVALID_ARG, "set_hints: the handle has already solved");
+    GG_HIP(hipSetDevice(r->device));
+    // wires 0 .. n_witness are ONE_WIRE and the witness (gg_r1cs_set_inputs, when called)
+    const size_t first_internal = r->expect_inputs >= 0 ? (size_t)r->expect_inputs + 1 : 1;
+    r->hints.init(r->nw, r->ncoef, r->ncons, first_internal, r->level_off.size() - 1, n_hints, hint_id, in_off,
+                  expr_off, term_wire, term_coeff, out_start, out_end, level_off, level_hints, n_levels);
     GG_CAPI_END
 }

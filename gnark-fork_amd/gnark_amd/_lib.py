@@ -191,6 +191,10 @@ def _load():
         "gg_scs_solution_dev": ([P, PP, PP, PP, PP], I),
         "gg_r1cs_schedule": ([P, ctypes.POINTER(I), ctypes.POINTER(S), ctypes.POINTER(S)], I),
         "gg_scs_schedule": ([P, ctypes.POINTER(I), ctypes.POINTER(S), ctypes.POINTER(S)], I),
+        "gg_hint_supported": ([ctypes.c_uint32, ctypes.POINTER(I), ctypes.POINTER(ctypes.c_char_p)], I),
+        "gg_hint_eval_host": ([I, ctypes.c_uint32, P, S, P, S], I),
+        "gg_r1cs_set_hints": ([P, S, P, P, P, P, P, P, P, P, P, S], I),
+        "gg_scs_set_hints": ([P, S, P, P, P, P, P, P, P, P, P, S], I),
         "gg_profile_enable": ([I], I),
         "gg_profile_get": ([ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),
                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)], I),
@@ -257,6 +261,7 @@ EXPORTED = [
     "gg_plonk_pk_part_timings", "gg_groth16_mpk_peer_access", "gg_plonk_pk_peer_access",
     "gg_fr_evaluate_many", "gg_msm_batch_shape", "gg_set_wait_timeout", "gg_get_wait_timeout",
     "gg_wait_selftest", "gg_wait_selftest_device", "gg_task_selftest", "gg_release_task_queues",
+    "gg_hint_supported", "gg_hint_eval_host", "gg_r1cs_set_hints", "gg_scs_set_hints",
 ]
 
 

@@ -1,6 +1,8 @@
-"""R1CS solver on MI355X: mirror of cs.R1CS's Solve for BN254 circuits without
-hint calls (constraint/bn254/solver.go:418-608, system.go:64-104), the system
-resident in HBM and the solution left there for the prover.
+"""R1CS solver on MI355X: mirror of cs.R1CS's Solve (constraint/bn254/
+solver.go:418-608, system.go:64-104), the system resident in HBM and the
+solution left there for the prover.  Hint calls: gnark's own seven hints
+(HINT_IDS) run on the GPU, passed as ``hints=[Hint(...)]``; any other hint is
+refused (such systems keep gnark's host solver).
 
     sys = R1CS.from_terms(nb_public, nb_secret, n_wires, constraints)   # once
     sol = sys.solve(witness_values)            # -> groth16.Solution (on device)
@@ -14,6 +16,7 @@ the deepest internal wire it reads and places its unsolved wires there)."""
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import numpy as np
@@ -30,6 +33,163 @@ class UnsatisfiedConstraintError(RuntimeError):
     def __init__(self, cid: int, msg: str):
         super().__init__(msg)
         self.cid = cid
+
+
+_GNARK = "github.com/consensys/gnark/"
+HINT_NAMES = (
+    _GNARK + "constraint/solver.InvZeroHint",
+    _GNARK + "std/math/bits.ithBit",
+    _GNARK + "std/math/bits.nBits",
+    _GNARK + "std/math/bits.nTrits",
+    _GNARK + "std/math/bits.nNaf",
+    _GNARK + "std/math/cmp.minOutputHint",
+    _GNARK + "std/math/cmp.isLessOutputHint",
+)
+
+
+def hint_id(go_name: str) -> int:
+    """solver.GetHintID: FNV-1a-32 of the Go function name (constraint/solver/hint.go:87-96)."""
+    h = 0x811C9DC5
+    for c in go_name.encode():
+        h = ((h ^ c) * 0x01000193) & 0xFFFFFFFF
+    return h
+
+
+# the hints the GPU solvers evaluate (gg_hint_supported), name -> HintID
+HINT_IDS = {name: hint_id(name) for name in HINT_NAMES}
+
+
+@dataclass
+class Hint:
+    """One hint instruction (constraint.HintMapping): ``inputs`` are linear
+    expressions [(wire, coeff int), ...] (a constant: (0, k) in an R1CS, whose
+    wire 0 is ONE_WIRE, or (CONST_WIRE, k) in either system), the outputs are
+    wires out_start .. out_end - 1, and ``before`` is the index of the constraint
+    it precedes in instruction order (len(constraints): after the last one)."""
+    hint_id: int
+    inputs: list
+    out_start: int
+    out_end: int
+    before: int
+
+
+CONST_WIRE = 0xFFFFFFFF  # a constant term of a hint input (Term.IsConstant)
+
+
+def hint_supported(hid: int):
+    """(supported, Go name or None) of gg_hint_supported."""
+    ok, name = ctypes.c_int(), ctypes.c_char_p()
+    check(lib.gg_hint_supported(hid, ctypes.byref(ok), ctypes.byref(name)))
+    return bool(ok.value), name.value.decode() if name.value else None
+
+
+def hint_eval_host(curve: str, hid: int, inputs: Sequence[int], n_out: int) -> list:
+    """One hint on the CPU by the library's own arithmetic (gg_hint_eval_host):
+    inputs and the returned outputs are integers in [0, r)."""
+    from ._lib import GG_CURVE_BN254, GG_CURVE_BLS12_381
+    bn = curve == "bn254"
+    mont, unmont, mod = (fr.fr_mont, fr.fr_unmont, fr.R) if bn else (fr.bls_fr_mont, fr.bls_fr_unmont, fr.BLS_R)
+    ibuf = b"".join(mont(int(v) % mod) for v in inputs) or bytes(32)
+    obuf = bytearray(32 * max(n_out, 1))
+    check(lib.gg_hint_eval_host(GG_CURVE_BN254 if bn else GG_CURVE_BLS12_381, hid, ptr(ibuf), len(inputs),
+                                ptr(obuf), n_out))
+    return [unmont(bytes(obuf[32 * i:32 * i + 32])) for i in range(n_out)]
+
+
+def _hint_order(hints, n_constraints):
+    """Instruction order: ("h", i) / ("c", j), hint i just before constraint hints[i].before."""
+    at = [[] for _ in range(n_constraints + 1)]
+    for i, h in enumerate(hints):
+        if not 0 <= h.before <= n_constraints:
+            raise ValueError("hint %d: before=%d outside [0, %d]" % (i, h.before, n_constraints))
+        at[h.before].append(i)
+    for c in range(n_constraints + 1):
+        for i in at[c]:
+            yield "h", i
+        if c < n_constraints:
+            yield "c", c
+
+
+def _place_hint(level, nb_inputs, h):
+    """BlueprintGenericHint.UpdateInstructionTree (blueprint_hint.go:75-106): the
+    outputs sit one level above the deepest input wire."""
+    mx = -1
+    for expr in h.inputs:
+        for w, _ in expr:
+            if w == CONST_WIRE or w < nb_inputs:
+                continue
+            if level[w] > mx:
+                mx = int(level[w])
+    mx += 1
+    level[h.out_start:h.out_end] = mx
+    return mx
+
+
+def _levels_with_hints(nb_inputs, n_wires, n_constraints, hints, cons_wires):
+    level = np.full(n_wires, -1, dtype=np.int64)
+    cl, hl = [], []
+    for kind, i in _hint_order(hints, n_constraints):
+        if kind == "h":
+            mx, dst = _place_hint(level, nb_inputs, hints[i]), hl
+        else:
+            mx, outs, dst = -1, [], cl
+            for w in cons_wires(i):
+                w = int(w)
+                if w < nb_inputs:
+                    continue
+                if level[w] < 0:
+                    if w not in outs:
+                        outs.append(w)
+                elif level[w] > mx:
+                    mx = int(level[w])
+            mx += 1
+            for w in outs:
+                level[w] = mx
+        while len(cl) <= mx:
+            cl.append([])
+            hl.append([])
+        dst[mx].append(i)
+    return cl, hl
+
+
+def compute_levels_with_hints(nb_inputs: int, n_wires: int, term_off, term_wire, hints) -> tuple:
+    """r1cs.Levels of a system with hint instructions, split into the constraints
+    and the hints of each level (two lists of the same length): hints and R1Cs
+    walked in instruction order (blueprint_hint.go:75-106, blueprint_r1cs.go:61-96)."""
+    ncons = (len(term_off) - 1) // 3
+    return _levels_with_hints(nb_inputs, n_wires, ncons, hints,
+                              lambda c: term_wire[int(term_off[3 * c]):int(term_off[3 * c + 3])])
+
+
+def compute_scs_levels_with_hints(nb_inputs: int, n_wires: int, wires, hints) -> tuple:
+    """compute_levels_with_hints for a sparse R1CS (xa, xb, xc per constraint)."""
+    w = np.asarray(wires, dtype=np.int64).reshape(-1, 3)
+    return _levels_with_hints(nb_inputs, n_wires, len(w), hints, lambda c: w[c])
+
+
+def _hint_arrays(hints, hint_levels, coeff_index):
+    """The gg_*_set_hints arrays; coeff_index(k) -> index into the handle's table."""
+    u32 = lambda x: np.ascontiguousarray(x, dtype=np.uint32)
+    ids, in_off, expr_off, tw, tc, o0, o1 = [], [0], [0], [], [], [], []
+    for h in hints:
+        ids.append(h.hint_id)
+        for expr in h.inputs:
+            for w, k in expr:
+                tw.append(w)
+                tc.append(coeff_index(k))
+            expr_off.append(len(tw))
+        in_off.append(len(expr_off) - 1)
+        o0.append(h.out_start)
+        o1.append(h.out_end)
+    lo = np.zeros(len(hint_levels) + 1, dtype=np.uint32)
+    lo[1:] = np.cumsum([len(x) for x in hint_levels])
+    lh = [i for lv in hint_levels for i in lv]
+    return [u32(a) for a in (ids, in_off, expr_off, tw, tc, o0, o1, lo, lh)], len(hint_levels)
+
+
+def _set_hints(fn, handle, hints, hint_levels, coeff_index):
+    arrs, n_levels = _hint_arrays(hints, hint_levels, coeff_index)
+    check(fn(handle, len(hints), *(ptr(a) for a in arrs), n_levels))
 
 
 def _schedule(fn, handle):
@@ -69,7 +229,7 @@ class R1CS:
 
     def __init__(self, nb_public: int, nb_secret: int, n_wires: int, term_off, term_wire, term_coeff,
                  coeffs: Sequence[int], levels: Optional[Sequence[Sequence[int]]] = None,
-                 curve: str = "bn254"):
+                 curve: str = "bn254", hints=None, hint_levels=None):
         from ._lib import GG_CURVE_BN254, GG_CURVE_BLS12_381
         self.curve = curve
         self.mod = fr.R if curve == "bn254" else fr.BLS_R
@@ -79,9 +239,13 @@ class R1CS:
         self.term_wire = np.ascontiguousarray(term_wire, dtype=np.uint32)
         self.term_coeff = np.ascontiguousarray(term_coeff, dtype=np.uint32)
         self.n_constraints = (len(self.term_off) - 1) // 3
+        self.hints = list(hints) if hints else None
+        if self.hints and (levels is None or hint_levels is None):
+            levels, hint_levels = compute_levels_with_hints(nb_public + nb_secret, n_wires, self.term_off,
+                                                            self.term_wire, self.hints)
         if levels is None:
             levels = compute_levels(nb_public + nb_secret, n_wires, self.term_off, self.term_wire)
-        self.levels = levels
+        self.levels, self.hint_levels = levels, hint_levels
         lo = np.zeros(len(levels) + 1, dtype=np.uint32)
         lo[1:] = np.cumsum([len(x) for x in levels])
         lc = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint32) for x in levels])
@@ -95,11 +259,20 @@ class R1CS:
         self.handle = h
         # newSolver's witness-size check, enforced by the library too (solver.go:71-76)
         check(lib.gg_r1cs_set_inputs(h, nb_public, nb_secret))
+        if self.hints:
+            index = {int(k) % self.mod: i for i, k in reversed(list(enumerate(coeffs)))}
+            self.set_hints(self.hints, hint_levels, lambda k: index[int(k) % self.mod])
+
+    def set_hints(self, hints, hint_levels, coeff_index):
+        """gg_r1cs_set_hints: once, before the first solve."""
+        _set_hints(lib.gg_r1cs_set_hints, self.handle, hints, hint_levels, coeff_index)
 
     @classmethod
     def from_terms(cls, nb_public: int, nb_secret: int, n_wires: int, constraints, levels=None,
-                   curve: str = "bn254") -> "R1CS":
-        """constraints: [(L, R, O)] with L = [(wire, coeff int), ...]."""
+                   curve: str = "bn254", hints=None, hint_levels=None) -> "R1CS":
+        """constraints: [(L, R, O)] with L = [(wire, coeff int), ...]; hints: [Hint]
+        (their coefficients join the same table; levels / hint_levels default to
+        compute_levels_with_hints)."""
         mod = fr.R if curve == "bn254" else fr.BLS_R
         table, index = [], {}
         off, wires, cids = [0], [], []
@@ -113,9 +286,16 @@ class R1CS:
                     wires.append(w)
                     cids.append(index[k])
                 off.append(len(wires))
+        for h in hints or ():
+            for expr in h.inputs:
+                for _, k in expr:
+                    k %= mod
+                    if k not in index:
+                        index[k] = len(table)
+                        table.append(k)
         if not table:
             table = [1]
-        return cls(nb_public, nb_secret, n_wires, off, wires, cids, table, levels, curve)
+        return cls(nb_public, nb_secret, n_wires, off, wires, cids, table, levels, curve, hints, hint_levels)
 
     def info(self):
         a, b, c = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
@@ -217,7 +397,7 @@ class SparseR1CS:
     L, R, O columns of evaluateLROSmallDomain (system.go:221-264)."""
 
     def __init__(self, nb_public: int, nb_secret: int, n_wires: int, wires, qidx, coeffs: Sequence[int],
-                 flags=None, levels=None, curve: str = "bls12-381"):
+                 flags=None, levels=None, curve: str = "bls12-381", hints=None, hint_levels=None):
         from ._lib import GG_CURVE_BN254, GG_CURVE_BLS12_381
         self.curve = curve
         self.mod = fr.BLS_R if curve == "bls12-381" else fr.R
@@ -228,9 +408,13 @@ class SparseR1CS:
         self.qidx = np.ascontiguousarray(qidx, dtype=np.uint32)
         self.n_constraints = len(self.wires) // 3
         self.flags = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        self.hints = list(hints) if hints else None
+        if self.hints and (levels is None or hint_levels is None):
+            levels, hint_levels = compute_scs_levels_with_hints(nb_public + nb_secret, n_wires, self.wires,
+                                                                self.hints)
         if levels is None:
             levels = compute_scs_levels(nb_public + nb_secret, n_wires, self.wires)
-        self.levels = levels
+        self.levels, self.hint_levels = levels, hint_levels
         lo = np.zeros(len(levels) + 1, dtype=np.uint32)
         lo[1:] = np.cumsum([len(x) for x in levels])
         lc = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint32) for x in levels])
@@ -242,14 +426,22 @@ class SparseR1CS:
                                 ctypes.byref(h)))
         self.handle = h
         check(lib.gg_scs_set_inputs(h, nb_public, nb_secret))
+        if self.hints:
+            index = {int(k) % self.mod: i for i, k in reversed(list(enumerate(coeffs)))}
+            self.set_hints(self.hints, hint_levels, lambda k: index[int(k) % self.mod])
         d = ctypes.c_size_t()
         check(lib.gg_scs_info(h, None, None, ctypes.byref(d)))
         self.domain = d.value
 
+    def set_hints(self, hints, hint_levels, coeff_index):
+        """gg_scs_set_hints: once, before the first solve."""
+        _set_hints(lib.gg_scs_set_hints, self.handle, hints, hint_levels, coeff_index)
+
     @classmethod
     def from_constraints(cls, nb_public: int, nb_secret: int, n_wires: int, constraints, flags=None,
-                         levels=None, curve: str = "bls12-381") -> "SparseR1CS":
-        """constraints: [(xa, xb, xc, qL, qR, qO, qM, qC)] with int coefficients."""
+                         levels=None, curve: str = "bls12-381", hints=None, hint_levels=None) -> "SparseR1CS":
+        """constraints: [(xa, xb, xc, qL, qR, qO, qM, qC)] with int coefficients;
+        hints: [Hint] (no ONE_WIRE here: a constant term is (CONST_WIRE, k))."""
         mod = fr.BLS_R if curve == "bls12-381" else fr.R
         table, index = [0, 1], {0: 0, 1: 1}
         wires, qidx = [], []
@@ -261,7 +453,14 @@ class SparseR1CS:
                     index[k] = len(table)
                     table.append(k)
                 qidx.append(index[k])
-        return cls(nb_public, nb_secret, n_wires, wires, qidx, table, flags, levels, curve)
+        for h in hints or ():
+            for expr in h.inputs:
+                for _, k in expr:
+                    k %= mod
+                    if k not in index:
+                        index[k] = len(table)
+                        table.append(k)
+        return cls(nb_public, nb_secret, n_wires, wires, qidx, table, flags, levels, curve, hints, hint_levels)
 
     def solve(self, witness, on_device: bool = True):
         """spr.Solve(fullWitness) -> (W, L, R, O): host bytes or DeviceBuffers."""

@@ -19,11 +19,15 @@ import (
 )
 
 // deviceSolver is r1cs.Solve on the GPU (constraint/bls12-381/solver.go:418-608)
-// for systems without hint calls: the R1Cs, the coefficient table and the
-// levels are uploaded once (gg_r1cs_create_ex, BLS12-381 fr), and a solve leaves W, A, B, C in
+// for systems whose hint calls are all gnark's built-in ones (gg_hint_supported;
+// none at all included): the R1Cs, the hint instructions, the coefficient table
+// and the levels are uploaded once (gg_r1cs_create_ex, BLS12-381 fr), and a solve leaves W, A, B, C in
 // HBM for gg_groth16_prove (inputs_on_device = 1) -- only the witness crosses
-// PCIe.  Built lazily next to setupDevicePointers; nil for systems with hints
-// (hints are Go functions: those keep gnark's solver).  A multi-GPU key has one
+// PCIe.  Built lazily next to setupDevicePointers; nil for systems with any
+// other hint (user-defined, BSB22 commitment, emulated arithmetic, lookup,
+// selector: hints are Go functions, those keep gnark's solver).  The caller
+// asks for a device solver only when the prover got no solver options, so no
+// option can override or add a function for one of the system's hint ids.  A multi-GPU key has one
 // solver per device, each leaving the whole solution on its GPU
 // (gg_groth16_mpk_prove_ex reads shard r's copy on devices[r]).
 type deviceSolver struct {
@@ -33,15 +37,66 @@ type deviceSolver struct {
 	nbInputs int // witness length: nbPublic - 1 + nbSecret (solver.go:71-76)
 }
 
-// newDeviceSolvers builds the CSR form of a hint-free system once and uploads
-// it to every distinct device of devs (nil map: the system has hints).
+// hintArrays is the system's hint instructions in the layout of
+// gg_r1cs_set_hints (BlueprintGenericHint.DecompressHint of each).
+type hintArrays struct {
+	ids, inOff, exprOff, wires, coeffs, outStart, outEnd []uint32
+}
+
+func (ha *hintArrays) add(hm *constraint.HintMapping) {
+	ha.ids = append(ha.ids, uint32(hm.HintID))
+	for _, le := range hm.Inputs {
+		for _, t := range le {
+			w := uint32(t.WireID())
+			if t.IsConstant() { // coeff * ONE_WIRE (term.go:35-41)
+				w = 0
+			}
+			ha.wires = append(ha.wires, w)
+			ha.coeffs = append(ha.coeffs, uint32(t.CoeffID()))
+		}
+		ha.exprOff = append(ha.exprOff, uint32(len(ha.wires)))
+	}
+	ha.inOff = append(ha.inOff, uint32(len(ha.exprOff)-1))
+	ha.outStart = append(ha.outStart, hm.OutputRange.Start)
+	ha.outEnd = append(ha.outEnd, hm.OutputRange.End)
+}
+
+// u32p is &s[0], or nil for an empty slice.
+func u32p(s []uint32) *C.uint32_t {
+	if len(s) == 0 {
+		return nil
+	}
+	return (*C.uint32_t)(unsafe.Pointer(&s[0]))
+}
+
+// newDeviceSolvers builds the CSR form of the system once and uploads it to
+// every distinct device of devs (nil map: the system has a hint the library
+// does not evaluate, or an instruction that is neither an R1C nor a hint).
 func newDeviceSolvers(sys *cs.R1CS, devs []int) (map[int]*deviceSolver, error) {
-	for _, inst := range sys.Instructions {
-		if _, ok := sys.Blueprints[inst.BlueprintID].(constraint.BlueprintHint); ok {
+	// instruction ids are not constraint ids once hints are in: an R1C
+	// instruction maps to its constraint index, a hint instruction to its
+	// hint index (r1cs.Levels holds instruction ids)
+	const isHint = uint32(1) << 31
+	instTo := make([]uint32, len(sys.Instructions))
+	ha := hintArrays{inOff: []uint32{0}, exprOff: []uint32{0}}
+	var hm constraint.HintMapping
+	for i, pi := range sys.Instructions {
+		switch bp := sys.Blueprints[pi.BlueprintID].(type) {
+		case constraint.BlueprintHint:
+			bp.DecompressHint(&hm, pi.Unpack(&sys.System))
+			var ok C.int
+			if C.gg_hint_supported(C.uint32_t(hm.HintID), &ok, nil) != C.GG_OK || ok == 0 {
+				return nil, nil // not one of gnark's built-in hints: gnark's solver
+			}
+			instTo[i] = isHint | uint32(len(ha.ids))
+			ha.add(&hm)
+		case constraint.BlueprintR1C:
+			instTo[i] = pi.ConstraintOffset // one R1C per instruction
+		default:
 			return nil, nil
 		}
 	}
-	rs := sys.GetR1Cs() // one R1C per instruction: instruction ids == constraint ids
+	rs := sys.GetR1Cs()
 	off := make([]uint32, 1, 3*len(rs)+1)
 	var wires, coeffs []uint32
 	for _, c := range rs {
@@ -59,11 +114,18 @@ func newDeviceSolvers(sys *cs.R1CS, devs []int) (map[int]*deviceSolver, error) {
 	}
 	levelOff := make([]uint32, 1, len(sys.Levels)+1)
 	levelCons := make([]uint32, 0, len(rs))
+	hintLevelOff := make([]uint32, 1, len(sys.Levels)+1)
+	hintLevel := make([]uint32, 0, len(ha.ids))
 	for _, l := range sys.Levels {
 		for _, iID := range l {
-			levelCons = append(levelCons, uint32(iID))
+			if to := instTo[iID]; to&isHint != 0 {
+				hintLevel = append(hintLevel, to&^isHint)
+			} else {
+				levelCons = append(levelCons, to)
+			}
 		}
 		levelOff = append(levelOff, uint32(len(levelCons)))
+		hintLevelOff = append(hintLevelOff, uint32(len(hintLevel)))
 	}
 	nbPublic, nbSecret := sys.GetNbPublicVariables(), sys.GetNbSecretVariables()
 	nbWires := nbPublic + nbSecret + sys.NbInternalVariables
@@ -86,6 +148,12 @@ func newDeviceSolvers(sys *cs.R1CS, devs []int) (map[int]*deviceSolver, error) {
 			}
 			// the library rejects a witness of another size too (a second line of defence)
 			if C.gg_r1cs_set_inputs(h, C.size_t(nbPublic), C.size_t(nbSecret)) != C.GG_OK {
+				C.gg_r1cs_release(h)
+				return lastError()
+			}
+			if len(ha.ids) > 0 && C.gg_r1cs_set_hints(h, C.size_t(len(ha.ids)), u32p(ha.ids), u32p(ha.inOff),
+				u32p(ha.exprOff), u32p(ha.wires), u32p(ha.coeffs), u32p(ha.outStart), u32p(ha.outEnd),
+				u32p(hintLevelOff), u32p(hintLevel), C.size_t(len(sys.Levels))) != C.GG_OK {
 				C.gg_r1cs_release(h)
 				return lastError()
 			}

@@ -19,28 +19,80 @@ import (
 	cs "github.com/consensys/gnark/constraint/bn254"
 )
 
-// scsSolver is spr.Solve on the GPU for sparse-R1CS without hint calls
+// scsSolver is spr.Solve on the GPU for sparse-R1CS whose hint calls are all
+// gnark's built-in ones (gg_hint_supported; none at all included)
 // (blueprint_scs.go:53-151 per level + evaluateLROSmallDomain, system.go:221-264):
 // the constraints (DecompressSparseR1C of every instruction), spr.Coefficients
-// and spr.Levels uploaded once (gg_scs_create); a solve leaves L, R, O in HBM
-// for gg_plonk_prove (inputs on device).  nil for systems with hints.
+// and spr.Levels uploaded once (gg_scs_create, gg_scs_set_hints); a solve
+// leaves L, R, O in HBM for gg_plonk_prove (inputs on device).  nil for systems
+// with any other hint (user-defined, BSB22 commitment, emulated arithmetic,
+// lookup, selector: those keep gnark's solver).  The caller asks for it only
+// when the prover got no solver options, so no option can override or add a
+// function for one of the system's hint ids.
 type scsSolver struct {
 	h C.gg_scs_t
 }
 
-var amdSolvers sync.Map // *ProvingKey -> *scsSolver (nil: the system has hints)
+var amdSolvers sync.Map // *ProvingKey -> *scsSolver (nil: a hint the library does not evaluate)
+
+// hintArrays is the system's hint instructions in the layout of
+// gg_scs_set_hints (BlueprintGenericHint.DecompressHint of each).
+type hintArrays struct {
+	ids, inOff, exprOff, wires, coeffs, outStart, outEnd []uint32
+}
+
+func (ha *hintArrays) add(hm *constraint.HintMapping) {
+	ha.ids = append(ha.ids, uint32(hm.HintID))
+	for _, le := range hm.Inputs {
+		for _, t := range le {
+			// a constant term keeps VID = MaxUint32: the coefficient alone (no ONE_WIRE here)
+			ha.wires = append(ha.wires, t.VID)
+			ha.coeffs = append(ha.coeffs, uint32(t.CoeffID()))
+		}
+		ha.exprOff = append(ha.exprOff, uint32(len(ha.wires)))
+	}
+	ha.inOff = append(ha.inOff, uint32(len(ha.exprOff)-1))
+	ha.outStart = append(ha.outStart, hm.OutputRange.Start)
+	ha.outEnd = append(ha.outEnd, hm.OutputRange.End)
+}
+
+// u32p is &s[0], or nil for an empty slice.
+func u32p(s []uint32) *C.uint32_t {
+	if len(s) == 0 {
+		return nil
+	}
+	return (*C.uint32_t)(unsafe.Pointer(&s[0]))
+}
 
 func newScsSolver(spr *cs.SparseR1CS) (*scsSolver, error) {
-	n := len(spr.Instructions)
-	wires := make([]uint32, 0, 3*n)
-	qidx := make([]uint32, 0, 5*n)
-	flags := make([]uint8, 0, n)
+	// instruction ids are not constraint ids once hints are in: a constraint
+	// instruction maps to its constraint index, a hint instruction to its
+	// hint index (spr.Levels holds instruction ids)
+	const isHint = uint32(1) << 31
+	nInst := len(spr.Instructions)
+	instTo := make([]uint32, nInst)
+	ha := hintArrays{inOff: []uint32{0}, exprOff: []uint32{0}}
+	var hm constraint.HintMapping
+	wires := make([]uint32, 0, 3*nInst)
+	qidx := make([]uint32, 0, 5*nInst)
+	flags := make([]uint8, 0, nInst)
 	var c constraint.SparseR1C
-	for _, inst := range spr.Instructions {
+	for i, inst := range spr.Instructions {
+		if bh, ok := spr.Blueprints[inst.BlueprintID].(constraint.BlueprintHint); ok {
+			bh.DecompressHint(&hm, inst.Unpack(&spr.System))
+			var sup C.int
+			if C.gg_hint_supported(C.uint32_t(hm.HintID), &sup, nil) != C.GG_OK || sup == 0 {
+				return nil, nil // not one of gnark's built-in hints (the BSB22 one included): gnark's solver
+			}
+			instTo[i] = isHint | uint32(len(ha.ids))
+			ha.add(&hm)
+			continue
+		}
 		bc, ok := spr.Blueprints[inst.BlueprintID].(constraint.BlueprintSparseR1C)
 		if !ok {
-			return nil, nil // a hint (or another non-constraint instruction): keep gnark's solver
+			return nil, nil // another non-constraint instruction: keep gnark's solver
 		}
+		instTo[i] = uint32(len(flags))
 		bc.DecompressSparseR1C(&c, inst.Unpack(&spr.System))
 		wires = append(wires, c.XA, c.XB, c.XC)
 		qidx = append(qidx, c.QL, c.QR, c.QO, c.QM, c.QC)
@@ -50,13 +102,21 @@ func newScsSolver(spr *cs.SparseR1CS) (*scsSolver, error) {
 		}
 		flags = append(flags, f)
 	}
+	n := len(flags)
 	levelOff := make([]uint32, 1, len(spr.Levels)+1)
 	levelCons := make([]uint32, 0, n)
-	for _, l := range spr.Levels { // instruction ids == constraint ids without hints
+	hintLevelOff := make([]uint32, 1, len(spr.Levels)+1)
+	hintLevel := make([]uint32, 0, len(ha.ids))
+	for _, l := range spr.Levels {
 		for _, iID := range l {
-			levelCons = append(levelCons, uint32(iID))
+			if to := instTo[iID]; to&isHint != 0 {
+				hintLevel = append(hintLevel, to&^isHint)
+			} else {
+				levelCons = append(levelCons, to)
+			}
 		}
 		levelOff = append(levelOff, uint32(len(levelCons)))
+		hintLevelOff = append(hintLevelOff, uint32(len(hintLevel)))
 	}
 	if n == 0 || len(spr.Coefficients) == 0 {
 		return nil, nil
@@ -72,6 +132,12 @@ func newScsSolver(spr *cs.SparseR1CS) (*scsSolver, error) {
 	}
 	// the library rejects a witness of another size too (solver.go:71-76)
 	if C.gg_scs_set_inputs(h, C.size_t(spr.GetNbPublicVariables()), C.size_t(spr.GetNbSecretVariables())) != C.GG_OK {
+		C.gg_scs_release(h)
+		return nil, amdError()
+	}
+	if len(ha.ids) > 0 && C.gg_scs_set_hints(h, C.size_t(len(ha.ids)), u32p(ha.ids), u32p(ha.inOff),
+		u32p(ha.exprOff), u32p(ha.wires), u32p(ha.coeffs), u32p(ha.outStart), u32p(ha.outEnd),
+		u32p(hintLevelOff), u32p(hintLevel), C.size_t(len(spr.Levels))) != C.GG_OK {
 		C.gg_scs_release(h)
 		return nil, amdError()
 	}

@@ -748,7 +748,7 @@ int gg_fr_from_canonical_be(int curve, const void *in_dev, void *out_dev, size_t
                             uint64_t *n_invalid, void *hip_stream);
 int gg_fr_to_canonical_be(int curve, const void *in_dev, void *out_dev, size_t n, void *hip_stream);
 
-/* ---- R1CS solver (constraint/bn254/solver.go:418-608, R1CS without hints)
+/* ---- R1CS solver (constraint/bn254/solver.go:418-608)
  * replaces r1cs.Solve(fullWitness) -> R1CSSolution{W, A, B, C} (prove.go:119-126,
  * system.go:64-104) on the GPU, leaving the solution in HBM for gg_groth16_prove
  * (inputs_on_device = 1).  The system in CSR form, as gnark's public API gives it:
@@ -761,7 +761,10 @@ int gg_fr_to_canonical_be(int curve, const void *in_dev, void *out_dev, size_t n
  *   (n_constraints) copied to the caller's buffers when non-null (host or device
  *   per out_on_device).  GG_ERR_UNSATISFIED: *unsatisfied = the first failing
  *   constraint (-1 when every constraint holds but wires were left unsolved).
- *   Circuits with hint calls solve on the host (gnark's solver). BN254 only. */
+ *   Hint calls: the seven hints gnark itself registers are evaluated on the GPU
+ *   (gg_r1cs_set_hints below); a system with any other hint (user-defined,
+ *   BSB22 commitment, emulated arithmetic, lookup, selector) solves on the host
+ *   (gnark's solver).  BN254 or BLS12-381 fr (gg_r1cs_create_ex). */
 typedef struct gg_r1cs *gg_r1cs_t;
 int gg_r1cs_create(size_t n_wires, size_t n_constraints, const uint32_t *term_off,
                    const uint32_t *term_wire, const uint32_t *term_coeff, const void *coeffs,
@@ -791,11 +794,60 @@ int gg_r1cs_solution_dev(gg_r1cs_t r, void **w, void **a, void **b, void **c);
  * *launches = kernel launches per solve, *segments = strand segments (threads) */
 int gg_r1cs_schedule(gg_r1cs_t r, int *strands, size_t *launches, size_t *segments);
 
+/* ---- gnark's built-in hints on the GPU (solveWithHint, solver.go:197-246)
+ * Recognised by HintID = FNV-1a-32 of the Go function name (constraint/solver/
+ * hint.go:87-96; the ids below are computed from that definition, no reference
+ * fixture pins them):                                        inputs / outputs
+ *   0x970c3c2f  constraint/solver.InvZeroHint     1 / 1    1/a mod r, 0 for a = 0
+ *   0xcc606925  std/math/bits.ithBit              2 / 1    bit inputs[1] of inputs[0]; 0 for
+ *                 an index that is no uint64, and for every index >= 256 -- also in
+ *                 [2^63, 2^64), where the reference's int() goes negative and panics
+ *   0xf54cdbeb  std/math/bits.nBits               1 / any  out[i] = bit i (0 for i >= 256)
+ *   0x7f90a7ad  std/math/bits.nTrits              1 / any  out[i] = base-3 digit i, zero padded
+ *   0x5ca55ec0  std/math/bits.nNaf                1 / any  NAF digits 0 / 1 / -1 (= r - 1), zero padded
+ *   0x7970dda3  std/math/cmp.minOutputHint        2 / 1    a if cmpInField(a, b) == -1, else b
+ *   0x73e09b3c  std/math/cmp.isLessOutputHint     2 / 1    1 if cmpInField(a, b) == -1, else 0
+ * gg_hint_supported: *supported = 1 and *go_name = the full Go name for these
+ *   ids, 0 and NULL otherwise (both nullable).
+ * gg_hint_eval_host: one hint on the CPU (no device needed), the code the
+ *   kernels run: inputs (n_in) and outputs (n_out) are fr Montgomery elements
+ *   of curve.  GG_ERR_UNSUPPORTED for another id, GG_ERR_INVALID_ARG when n_in
+ *   or n_out does not match the table.
+ * gg_r1cs_set_hints / gg_scs_set_hints: the system's hint instructions
+ *   (BlueprintGenericHint.DecompressHint), at most once per handle and before
+ *   its first solve:
+ *     in_off[h] .. in_off[h + 1]: the inputs of hint h; expr_off[i] .. expr_off[i + 1]:
+ *       the terms of input i (a linear expression; empty = 0); term_wire /
+ *       term_coeff: wire id and index into the handle's coeffs.  A constant term
+ *       is coefficient x wire 0 for an R1CS (ONE_WIRE), or wire 0xffffffff
+ *       (the coefficient alone) for either system;
+ *     out_start[h], out_end[h]: HintMapping.OutputRange;
+ *     level_off / level_hints: the hints of each level, n_levels and numbering
+ *       as the handle's (r1cs.Levels holds instruction ids: constraint
+ *       instructions go to the create call, hint instructions here).  A level
+ *       may hold only hints (its constraint level is then empty).
+ *   GG_ERR_UNSUPPORTED: an id outside the table (named in gg_last_error()).
+ *   GG_ERR_INVALID_ARG: a second call or a call after a solve, a hint not in
+ *   exactly one level, out_start > out_end, an output range that touches an
+ *   input wire, passes n_wires or overlaps another, a term index out of range,
+ *   an arity other than the table's.  A solve of a handle with hints runs one
+ *   launch per level (gg_*_schedule: *strands = 0) plus two per level that holds
+ *   hints; a hint that reads an unsolved wire fails the solve with
+ *   GG_ERR_INVALID_ARG "hint #k: input wire unsolved at its level (the levels do
+ *   not match the system)". */
+int gg_hint_supported(uint32_t hint_id, int *supported, const char **go_name);
+int gg_hint_eval_host(int curve, uint32_t hint_id, const void *inputs, size_t n_in,
+                      void *outputs, size_t n_out);
+int gg_r1cs_set_hints(gg_r1cs_t r, size_t n_hints, const uint32_t *hint_id, const uint32_t *in_off,
+                      const uint32_t *expr_off, const uint32_t *term_wire, const uint32_t *term_coeff,
+                      const uint32_t *out_start, const uint32_t *out_end, const uint32_t *level_off,
+                      const uint32_t *level_hints, size_t n_levels);
+
 /* ---- sparse-R1CS (PlonK) solver: the SCS blueprints' Solve
  * (constraint/blueprint_scs.go:53-151) level by level (solver.go:418-533) and
  * evaluateLROSmallDomain (constraint/bls12-381/system.go:221-264): replaces
  * spr.Solve(fullWitness) -> SparseR1CSSolution{L, R, O} (plonk prove.go:180-187)
- * for hint-free systems; L, R, O (domain = next power of two of
+ * (hint calls as for the R1CS solver: gg_scs_set_hints); L, R, O (domain = next power of two of
  * n_constraints + nb_public) stay in HBM for gg_plonk_prove (inputs_on_device).
  *   wires[3 c + 0..2] = xa, xb, xc; qidx[5 c + 0..4] = qL, qR, qO, qM, qC
  *   (indices into coeffs, fr Montgomery); flags[c] & 1: a BSB22 commitment
@@ -817,6 +869,11 @@ int gg_scs_solution_dev(gg_scs_t h, void **w, void **l, void **r, void **o);
 int gg_scs_schedule(gg_scs_t h, int *strands, size_t *launches, size_t *segments);
 /* the same check for a sparse R1CS: n_witness == nb_public + nb_secret */
 int gg_scs_set_inputs(gg_scs_t h, size_t nb_public, size_t nb_secret);
+/* gg_r1cs_set_hints for a sparse R1CS (no ONE_WIRE: a constant term is wire 0xffffffff) */
+int gg_scs_set_hints(gg_scs_t h, size_t n_hints, const uint32_t *hint_id, const uint32_t *in_off,
+                     const uint32_t *expr_off, const uint32_t *term_wire, const uint32_t *term_coeff,
+                     const uint32_t *out_start, const uint32_t *out_end, const uint32_t *level_off,
+                     const uint32_t *level_hints, size_t n_levels);
 
 /* ------------------------------------------------------------ profiling
  * Kernel-level timing with HIP events recorded on the stream each kernel is
