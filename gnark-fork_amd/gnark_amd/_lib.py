@@ -22,6 +22,12 @@ GG_G1, GG_G2, GG_BLS12_381_G1, GG_BLS12_381_G2 = 1, 2, 3, 4
 GG_CURVE_BN254, GG_CURVE_BLS12_381 = 0, 1
 PEER_ACCESS = {0: "same_device", 1: "enabled", 2: "unavailable", 3: "enable_failed"}  # GG_PEER_*
 GG_DIF, GG_DIT = 0, 1
+# gg_groth16_setup_layout classes and gg_groth16_setup_read parts
+GG_SETUP_CLASS_VK_K, GG_SETUP_CLASS_PK_K, GG_SETUP_CLASS_CK = 0, 1, 2
+(GG_SETUP_G1_A, GG_SETUP_G1_B, GG_SETUP_G1_K, GG_SETUP_G1_Z, GG_SETUP_G2_B, GG_SETUP_ALPHA1, GG_SETUP_BETA1,
+ GG_SETUP_DELTA1, GG_SETUP_BETA2, GG_SETUP_DELTA2, GG_SETUP_GAMMA2, GG_SETUP_VK_K, GG_SETUP_INFINITY_A,
+ GG_SETUP_INFINITY_B, GG_SETUP_K_WIRE_INDEX, GG_SETUP_PEDERSEN_VK) = range(16)
+GG_SETUP_CK_BASIS, GG_SETUP_CK_BASIS_SIGMA = 0x100, 0x200
 
 
 # gg_exchange_fn (include/gnark_amd.h): all-to-all supplied by the caller
@@ -195,6 +201,14 @@ def _load():
         "gg_hint_eval_host": ([I, ctypes.c_uint32, P, S, P, S], I),
         "gg_r1cs_set_hints": ([P, S, P, P, P, P, P, P, P, P, P, S], I),
         "gg_scs_set_hints": ([P, S, P, P, P, P, P, P, P, P, P, S], I),
+        "gg_groth16_setup_layout": ([S, S, P, S, P, P, P, P, ctypes.POINTER(S), ctypes.POINTER(S), P], I),
+        "gg_groth16_setup": ([I, S, S, S, P, P, P, P, S, P, S, P, P, P, P, P, P, P, P, P, P, P, P, PP], I),
+        "gg_groth16_setup_info": ([P, ctypes.POINTER(I), ctypes.POINTER(S), ctypes.POINTER(S), ctypes.POINTER(S),
+                                   ctypes.POINTER(S), ctypes.POINTER(S), ctypes.POINTER(S), P, S,
+                                   ctypes.POINTER(S), ctypes.POINTER(S)], I),
+        "gg_groth16_setup_read": ([P, I, P, S], I),
+        "gg_groth16_setup_timings": ([P, ctypes.POINTER(ctypes.c_double), I], I),
+        "gg_groth16_setup_release": ([P], I),
         "gg_profile_enable": ([I], I),
         "gg_profile_get": ([ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),
                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)], I),
@@ -262,6 +276,8 @@ EXPORTED = [
     "gg_fr_evaluate_many", "gg_msm_batch_shape", "gg_set_wait_timeout", "gg_get_wait_timeout",
     "gg_wait_selftest", "gg_wait_selftest_device", "gg_task_selftest", "gg_release_task_queues",
     "gg_hint_supported", "gg_hint_eval_host", "gg_r1cs_set_hints", "gg_scs_set_hints",
+    "gg_groth16_setup_layout", "gg_groth16_setup", "gg_groth16_setup_info", "gg_groth16_setup_read",
+    "gg_groth16_setup_timings", "gg_groth16_setup_release",
 ]
 
 

@@ -87,3 +87,29 @@ def bls_domain_generator(log_n: int) -> int:
     reference fixture; pass pk.Domain.Generator to mirror a real key)."""
     assert 0 <= log_n <= BLS_FR_TWO_ADICITY
     return pow(BLS_FR_MULTIPLICATIVE_GEN, (BLS_R - 1) >> log_n, BLS_R)
+
+
+# ---- curve.Generators() (setup.go:129): the standard generators of both curves
+# [ext: gnark-crypto ecc/bn254, ecc/bls12-381; EIP-197 and the BLS12-381 spec]
+G1_GEN = (1, 2)
+G2_GEN = ((0x1800DEEF121F1E76426A00665E5C4479674322D4F75EDADD46DEBD5CD992F6ED,
+           0x198E9393920D483A7260BFB731FB5D25F1AA493335A9E71297E485B7AEF312C2),
+          (0x12C85EA5DB8C6DEB4AAB71808DCB408FE3D1E7690C43D37B4CE6CC0166FA7DAA,
+           0x090689D0585FF075EC9E99AD690C3395BC4B313370B38EF355ACDADCD122975B))
+BLS_G1_GEN = (0x17F1D3A73197D7942695638C4FA9AC0FC3688C4F9774B905A14E3A3F171BAC586C55E83FF97A1AEFFB3AF00ADB22C6BB,
+              0x08B3F481E3AAA0F1A09E30ED741D8AE4FCF5E095D5D00AF600DB18CB2C04B3EDD03CC744A2888AE40CAA232946C5E7E1)
+BLS_G2_GEN = ((0x024AA2B2F08F0A91260805272DC51051C6E47AD4FA403B02B4510B647AE3D1770BAC0326A805BBEFD48056C8C121BDB8,
+               0x13E02B6052719F607DACD3A088274F65596BD0D09920B61AB5DA61BBDC7F5049334CF11213945D57E5AC7D055D042B7E),
+              (0x0CE5D527727D6E118CC9CDC6DA2E351AADFD9BAA8CBDD3A76D429A695160D12C923AC9CC3BACA289E193548608B82801,
+               0x0606C4A02EA734CC32ACD2B02BC28B99CB3E287E85A763AF267492AB572E99AB3F370D275CEC1DA1AAA9075FF05F79BE))
+
+
+def generators(curve: str = "bn254"):
+    """(G1Affine, G2Affine) of curve.Generators() in gnark's memory layout
+    (Montgomery, G2 as {X.A0, X.A1, Y.A0, Y.A1})."""
+    if curve == "bn254":
+        mont, g1, g2 = fp_mont, G1_GEN, G2_GEN
+    else:
+        mont, g1, g2 = bls_fp_mont, BLS_G1_GEN, BLS_G2_GEN
+    return (mont(g1[0]) + mont(g1[1]),
+            mont(g2[0][0]) + mont(g2[0][1]) + mont(g2[1][0]) + mont(g2[1][1]))

@@ -767,3 +767,192 @@ def prove_distributed_h(pk: ProvingKeyShard, hs: HShard, xchg: TorchExchange, so
     finally:
         xchg.guard = None
     return gather_and_finalize(pk.data, part, r, s, device, fixed=fixed, guard=guard)
+
+
+# ------------------------------------------------------------------- Setup
+@dataclasses.dataclass
+class VerifyingKeyData:
+    """Host copy of groth16.VerifyingKey (setup.go:63-82), gnark byte layouts.
+    e, deltaNeg and gammaNeg (vk.Precompute) are left to the verifier."""
+    alpha1: bytes
+    beta1: bytes
+    delta1: bytes
+    beta2: bytes
+    gamma2: bytes
+    delta2: bytes
+    K: bytes                                     # vk.G1.K: public wires then commitment wires
+    nb_public: int
+    commitment_key_g: Optional[bytes] = None     # pedersen.VerifyingKey.G (G2), with commitments
+    commitment_key_g_root_sigma_neg: Optional[bytes] = None
+    public_and_commitment_committed: Sequence = ()   # setup.go:295
+    curve: str = "bn254"
+
+
+@dataclasses.dataclass
+class ToxicWaste:
+    """sampleToxicWaste (setup.go:444-478): integers in [1, r)."""
+    tau: int
+    alpha: int
+    beta: int
+    gamma: int
+    delta: int
+
+
+def sample_toxic_waste(curve: str = "bn254") -> ToxicWaste:
+    mod = fr.R if curve == "bn254" else fr.BLS_R
+    return ToxicWaste(*(1 + secrets.randbelow(mod - 1) for _ in range(5)))
+
+
+def setup_layout(n_wires: int, nb_public: int, commitment_wires=(), private_committed=()):
+    """gg_groth16_setup_layout (host only): (wire_class, wire_slot, n_vk_k, n_pk_k,
+    [n_ck]) -- the K split of setup.go:159-196."""
+    nc = len(commitment_wires)
+    cw = np.ascontiguousarray(commitment_wires, dtype=np.uint32)
+    coff = np.zeros(nc + 1, dtype=np.uint32)
+    coff[1:] = np.cumsum([len(x) for x in private_committed])
+    cwire = np.ascontiguousarray([w for x in private_committed for w in x], dtype=np.uint32)
+    cls, slot = np.zeros(n_wires, dtype=np.uint32), np.zeros(n_wires, dtype=np.uint32)
+    nvk, npk = ctypes.c_size_t(), ctypes.c_size_t()
+    nck = (ctypes.c_size_t * max(nc, 1))()
+    check(lib.gg_groth16_setup_layout(n_wires, nb_public, ptr(cw) if nc else None, nc, ptr(coff) if nc else None,
+                                      ptr(cwire) if len(cwire) else None, ptr(cls), ptr(slot),
+                                      ctypes.byref(nvk), ctypes.byref(npk), nck))
+    return cls, slot, nvk.value, npk.value, list(nck)[:nc]
+
+
+class SetupResult:
+    """gg_groth16_setup's handle: the key's points in HBM until read."""
+
+    def __init__(self, handle, curve):
+        self.handle, self.curve = handle, curve
+        ln = ctypes.c_int()
+        v = [ctypes.c_size_t() for _ in range(8)]
+        nck = (ctypes.c_size_t * 256)()
+        check(lib.gg_groth16_setup_info(handle, ctypes.byref(ln), *(ctypes.byref(x) for x in v[:6]), nck, 256,
+                                        ctypes.byref(v[6]), ctypes.byref(v[7])))
+        self.log_n = ln.value
+        self.nA, self.nB, self.nK, self.nZ, self.n_vk_k, self.n_commitments, self.acc_chunk, self.acc_launches = \
+            (x.value for x in v)
+        self.n_ck = list(nck)[:self.n_commitments]
+
+    def read(self, which: int, nbytes: int) -> bytes:
+        out = bytearray(nbytes)
+        check(lib.gg_groth16_setup_read(self.handle, which, ptr(out) if nbytes else None, nbytes))
+        return bytes(out)
+
+    def timings(self) -> dict:
+        t = (ctypes.c_double * 9)()
+        check(lib.gg_groth16_setup_timings(self.handle, t, 9))
+        return dict(zip(["transpose", "lagrange", "accumulate", "kz", "g1", "g2", "accumulate_kernels",
+                         "accumulate_threads", "terms"], list(t)))
+
+    def close(self):
+        if self.handle:
+            lib.gg_groth16_setup_release(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def setup_device(nb_public: int, n_wires: int, term_off, term_wire, term_coeff, coeffs: Sequence[int],
+                 commitments=(), toxic_waste: Optional[ToxicWaste] = None, pedersen=None,
+                 curve: str = "bn254") -> SetupResult:
+    """gg_groth16_setup: the CSR arguments of solver.R1CS; the result stays in HBM
+    (SetupResult.read).  `setup` is this plus the read-back."""
+    bn = curve == "bn254"
+    mod, mont = (fr.R, fr.fr_mont) if bn else (fr.BLS_R, fr.bls_fr_mont)
+    off = np.ascontiguousarray(term_off, dtype=np.uint32)
+    wire = np.ascontiguousarray(term_wire, dtype=np.uint32)
+    cidx = np.ascontiguousarray(term_coeff, dtype=np.uint32)
+    ncons = (len(off) - 1) // 3
+    tw = toxic_waste if toxic_waste is not None else sample_toxic_waste(curve)
+    nc = len(commitments)
+    cw = np.ascontiguousarray([c[0] for c in commitments], dtype=np.uint32)
+    coff = np.zeros(nc + 1, dtype=np.uint32)
+    coff[1:] = np.cumsum([len(c[1]) for c in commitments])
+    cwire = np.ascontiguousarray([w for c in commitments for w in c[1]], dtype=np.uint32)
+    sigma = g = None
+    if nc:
+        sigma, g = pedersen if pedersen is not None else (1 + secrets.randbelow(mod - 1) for _ in range(2))
+        sigma, g = mont(sigma % mod), mont(g % mod)
+    log_n = max(ncons - 1, 0).bit_length()
+    omega = mont((fr.domain_generator if bn else fr.bls_domain_generator)(log_n))
+    g1, g2 = fr.generators(curve)
+    cbytes = b"".join(mont(int(k) % mod) for k in coeffs)
+    h = ctypes.c_void_p()
+    check(lib.gg_groth16_setup(
+        GG_CURVE_BN254 if bn else GG_CURVE_BLS12_381, n_wires, ncons, nb_public, ptr(off),
+        ptr(wire) if len(wire) else None, ptr(cidx) if len(cidx) else None, ptr(cbytes), len(coeffs),
+        ptr(cw) if nc else None, nc, ptr(coff) if nc else None, ptr(cwire) if len(cwire) else None,
+        ptr(mont(tw.tau % mod)), ptr(mont(tw.alpha % mod)), ptr(mont(tw.beta % mod)), ptr(mont(tw.gamma % mod)),
+        ptr(mont(tw.delta % mod)), ptr(sigma), ptr(g), ptr(omega), ptr(g1), ptr(g2), ctypes.byref(h)))
+    return SetupResult(h, curve)
+
+
+def setup(nb_public: int, n_wires: int, term_off, term_wire, term_coeff, coeffs: Sequence[int],
+          commitments=(), toxic_waste: Optional[ToxicWaste] = None, pedersen=None, curve: str = "bn254"):
+    """groth16.Setup (setup.go:85-337) on the GPU -> (ProvingKeyData, VerifyingKeyData).
+
+    The R1CS as solver.R1CS takes it (CSR terms + coefficient table of ints);
+    commitments: (commitment_wire, private_committed, public_and_commitment_committed)
+    per BSB22 commitment; toxic_waste / pedersen = (sigma, g) pin the randomness
+    (tests), otherwise they are sampled with `secrets`, zero rejected, as
+    sampleToxicWaste does.  The ProvingKeyData goes straight into ProvingKey(...)."""
+    from . import _lib as L
+    from . import pedersen as ped
+    res = setup_device(nb_public, n_wires, term_off, term_wire, term_coeff, coeffs, commitments, toxic_waste,
+                       pedersen, curve)
+    try:
+        g1b, g2b = _SIZES[curve]
+        rd = res.read
+        keys = None
+        if res.n_commitments:
+            keys = [ped.ProvingKey(rd(L.GG_SETUP_CK_BASIS + j, m * g1b), rd(L.GG_SETUP_CK_BASIS_SIGMA + j, m * g1b))
+                    for j, m in enumerate(res.n_ck)]
+        kidx = np.frombuffer(rd(L.GG_SETUP_K_WIRE_INDEX, 4 * res.nK), dtype=np.uint32)
+        alpha1, beta1, delta1 = (rd(w, g1b) for w in (L.GG_SETUP_ALPHA1, L.GG_SETUP_BETA1, L.GG_SETUP_DELTA1))
+        beta2, delta2, gamma2 = (rd(w, g2b) for w in (L.GG_SETUP_BETA2, L.GG_SETUP_DELTA2, L.GG_SETUP_GAMMA2))
+        pk = ProvingKeyData(
+            log_n=res.log_n, g1_A=rd(L.GG_SETUP_G1_A, res.nA * g1b), g1_B=rd(L.GG_SETUP_G1_B, res.nB * g1b),
+            g1_Z=rd(L.GG_SETUP_G1_Z, res.nZ * g1b), g1_K=rd(L.GG_SETUP_G1_K, res.nK * g1b),
+            alpha1=alpha1, beta1=beta1, delta1=delta1, g2_B=rd(L.GG_SETUP_G2_B, res.nB * g2b),
+            beta2=beta2, delta2=delta2, infinity_A=rd(L.GG_SETUP_INFINITY_A, n_wires),
+            infinity_B=rd(L.GG_SETUP_INFINITY_B, n_wires), nb_public=nb_public,
+            k_wire_index=kidx if res.n_commitments else None, curve=curve, commitment_keys=keys)
+        vk = VerifyingKeyData(alpha1=alpha1, beta1=beta1, delta1=delta1, beta2=beta2, gamma2=gamma2, delta2=delta2,
+                              K=rd(L.GG_SETUP_VK_K, res.n_vk_k * g1b), nb_public=nb_public, curve=curve)
+        if res.n_commitments:
+            pv = rd(L.GG_SETUP_PEDERSEN_VK, 2 * g2b)
+            vk.commitment_key_g, vk.commitment_key_g_root_sigma_neg = pv[:g2b], pv[g2b:]
+            # GetPublicAndCommitmentCommitted(commitmentWires, nbPublic) (commitment.go:53-74):
+            # public wires as they are, a committed commitment wire as its position after them
+            cws = [int(c[0]) for c in commitments]
+            vk.public_and_commitment_committed = [
+                [int(w) if w < nb_public else nb_public + cws.index(int(w)) for w in c[2]] for c in commitments]
+        return pk, vk
+    finally:
+        res.close()
+
+
+def setup_from_terms(nb_public: int, n_wires: int, constraints, **kw):
+    """setup for [(L, R, O)] constraint lists with L = [(wire, coeff int), ...]
+    (solver.R1CS.from_terms' input)."""
+    curve = kw.get("curve", "bn254")
+    mod = fr.R if curve == "bn254" else fr.BLS_R
+    table, index = [], {}
+    off, wires, cids = [0], [], []
+    for sides in constraints:
+        for side in sides:
+            for w, k in side:
+                k %= mod
+                if k not in index:
+                    index[k] = len(table)
+                    table.append(k)
+                wires.append(w)
+                cids.append(index[k])
+            off.append(len(wires))
+    return setup(nb_public, n_wires, off, wires, cids, table or [1], **kw)

@@ -23,3 +23,8 @@ func (pk *ProvingKey) Release() {}
 
 // deviceSolver exists only with the build tag (solver_amd.go); deviceInfo names it.
 type deviceSolver struct{}
+
+// Setup without the build tag is gnark's CPU Setup (setup.go:85-337).
+func Setup(r1cs *cs.R1CS, pk *ProvingKey, vk *groth16_bls12381.VerifyingKey) error {
+	return groth16_bls12381.Setup(r1cs, &pk.ProvingKey, vk)
+}

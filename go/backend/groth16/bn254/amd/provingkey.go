@@ -72,9 +72,7 @@ type ProvingKey struct {
 	*deviceInfo
 }
 
-func Setup(r1cs *cs.R1CS, pk *ProvingKey, vk *groth16_bn254.VerifyingKey) error {
-	return groth16_bn254.Setup(r1cs, &pk.ProvingKey, vk)
-}
+// Setup: setup_amd.go (the GPU Setup, build tag amd) or noamd.go (gnark's own).
 
 func DummySetup(r1cs *cs.R1CS, pk *ProvingKey) error {
 	return groth16_bn254.DummySetup(r1cs, &pk.ProvingKey)

@@ -875,6 +875,99 @@ int gg_scs_set_hints(gg_scs_t h, size_t n_hints, const uint32_t *hint_id, const 
                      const uint32_t *out_start, const uint32_t *out_end, const uint32_t *level_off,
                      const uint32_t *level_hints, size_t n_levels);
 
+/* ------------------------------------------------------------ Groth16 Setup
+ * groth16.Setup (backend/groth16/bn254/setup.go:85-337, the same file under
+ * bls12-381/) on the GPU: from the R1CS matrices and the toxic waste to the
+ * contents of gnark's ProvingKey and VerifyingKey, in gnark's memory layout.
+ * The R1CS is the CSR of gg_r1cs_create_ex (no handle: Setup needs only the
+ * matrices, so circuits whose hints keep the host solver are set up here too).
+ *
+ * The commitments (r1cs.CommitmentInfo, setup.go:99-108):
+ *   commitment_wires[n_commitments]   CommitmentIndexes(), strictly increasing
+ *   committed_off[j] .. committed_off[j + 1]  the private committed wires of
+ *     commitment j in committed_wire[] (GetPrivateCommitted()), each list
+ *     strictly increasing; NULL arrays when n_commitments == 0. */
+#define GG_SETUP_CLASS_VK_K 0 /* public or commitment wire: vk.G1.K, gamma^-1 */
+#define GG_SETUP_CLASS_PK_K 1 /* private wire: pk.G1.K, delta^-1 */
+#define GG_SETUP_CLASS_CK 2   /* 2 + j: private committed wire of commitment j (Pedersen basis j) */
+/* The K split of setup.go:159-196 (host only, no device call): per wire its
+ * class (GG_SETUP_CLASS_*) and its slot inside that class; *n_vk_k, *n_pk_k and
+ * n_ck[n_commitments] are the class sizes (outputs nullable).
+ * GG_ERR_INVALID_ARG, the message naming the wire: a list that is not strictly
+ * increasing, a committed or commitment wire below nb_public or at / above
+ * n_wires, a wire in two commitments (or both a commitment wire and privately
+ * committed: the reference's loop would stall on it). */
+int gg_groth16_setup_layout(size_t n_wires, size_t nb_public, const uint32_t *commitment_wires,
+                            size_t n_commitments, const uint32_t *committed_off,
+                            const uint32_t *committed_wire, uint32_t *wire_class, uint32_t *wire_slot,
+                            size_t *n_vk_k, size_t *n_pk_k, size_t *n_ck);
+
+typedef struct gg_g16_setup *gg_g16_setup_t;
+/* Setup (setup.go:85-337).  The caller passes the toxic waste (sampleToxicWaste,
+ * setup.go:444-478) as gg_groth16_prove takes r and s, so that tests can pin it:
+ * tau, alpha, beta, gamma, delta, and for a circuit with commitments
+ * pedersen_sigma and pedersen_g (pedersen.Setup's sigma; the Pedersen verifying
+ * key's G is pedersen_g * g2_gen), all fr Montgomery; the Pedersen pair may be
+ * NULL when n_commitments == 0.  As everywhere in this ABI the curve constants
+ * come from the caller: omega_mont = the generator of fft.NewDomain(n_constraints)
+ * (the next power of two, log_n <= 28; setup.go:111), g1_gen / g2_gen =
+ * curve.Generators() (affine, setup.go:129).
+ * GG_ERR_INVALID_ARG: a zero alpha, beta, gamma, delta or sigma; tau^n == 1
+ * ("tau is in the domain": the reference divides by zero there, setup.go:368-371);
+ * omega not of order n; a term wire >= n_wires or a coefficient id >= n_coeffs;
+ * everything gg_groth16_setup_layout refuses.
+ * Every device buffer that held toxic waste or discrete logs (the L_j(tau)
+ * table, A, B, C, the K and Z scalars, sigma * ckK, scan scratch) is overwritten
+ * with zeros before it is freed, on the error paths too. */
+int gg_groth16_setup(int curve, size_t n_wires, size_t n_constraints, size_t nb_public,
+                     const uint32_t *term_off, const uint32_t *term_wire, const uint32_t *term_coeff,
+                     const void *coeffs, size_t n_coeffs, const uint32_t *commitment_wires,
+                     size_t n_commitments, const uint32_t *committed_off, const uint32_t *committed_wire,
+                     const void *tau, const void *alpha, const void *beta, const void *gamma,
+                     const void *delta, const void *pedersen_sigma, const void *pedersen_g,
+                     const void *omega_mont, const void *g1_gen, const void *g2_gen,
+                     gg_g16_setup_t *out);
+/* sizes of the result (all outputs nullable): nA / nB = the non-infinity A / B
+ * points (setup.go:216-237), nK = len(pk.G1.K), nZ = 2^log_n - 1 (setup.go:266),
+ * n_vk_k = len(vk.G1.K), n_ck[j] for j < min(n_ck_cap, *n_commitments) = the
+ * Pedersen basis sizes.  *acc_chunk = the number of terms (or partial sums) one
+ * thread of the accumulation adds in sequence (setupABC, setup.go:411-430): a
+ * wire of degree d takes ceil(log_chunk d) rounds; *acc_launches = accumulation
+ * kernel launches of this setup. */
+int gg_groth16_setup_info(gg_g16_setup_t h, int *log_n, size_t *nA, size_t *nB, size_t *nK, size_t *nZ,
+                          size_t *n_vk_k, size_t *n_commitments, size_t *n_ck, size_t n_ck_cap,
+                          size_t *acc_chunk, size_t *acc_launches);
+/* parts of the result for gg_groth16_setup_read; points are affine in the
+ * curve's layout (gg_groth16_pk_create_ex) */
+#define GG_SETUP_G1_A 0        /* pk.G1.A, nA points (setup.go:259) */
+#define GG_SETUP_G1_B 1        /* pk.G1.B, nB */
+#define GG_SETUP_G1_K 2        /* pk.G1.K, nK (setup.go:274) */
+#define GG_SETUP_G1_Z 3        /* pk.G1.Z, bit-reversed and truncated to nZ (setup.go:265-267) */
+#define GG_SETUP_G2_B 4        /* pk.G2.B, nB (setup.go:310) */
+#define GG_SETUP_ALPHA1 5      /* [alpha]1 */
+#define GG_SETUP_BETA1 6       /* [beta]1 */
+#define GG_SETUP_DELTA1 7      /* [delta]1 */
+#define GG_SETUP_BETA2 8       /* [beta]2 */
+#define GG_SETUP_DELTA2 9      /* [delta]2 */
+#define GG_SETUP_GAMMA2 10     /* [gamma]2 (setup.go:318) */
+#define GG_SETUP_VK_K 11       /* vk.G1.K, n_vk_k (setup.go:271) */
+#define GG_SETUP_INFINITY_A 12 /* pk.InfinityA, one byte per wire (by value: e.IsZero(), setup.go:217-219) */
+#define GG_SETUP_INFINITY_B 13 /* pk.InfinityB */
+#define GG_SETUP_K_WIRE_INDEX 14 /* uint32[nK]: the wire of each pk.G1.K point (filterHeap, prove.go:238-248) */
+#define GG_SETUP_PEDERSEN_VK 15  /* two G2 points: G, GRootSigmaNeg = -sigma^-1 G (only with commitments) */
+#define GG_SETUP_CK_BASIS 0x100  /* + j: pedersen.ProvingKey.Basis of commitment j, n_ck[j] G1 points */
+#define GG_SETUP_CK_BASIS_SIGMA 0x200 /* + j: BasisExpSigma of commitment j */
+/* copies part `which` to out_host; bytes must be the part's exact size */
+int gg_groth16_setup_read(gg_g16_setup_t h, int which, void *out_host, size_t bytes);
+/* wall ms of the phases of that setup (each ended by a stream wait): 0 transpose
+ * (validation + per-wire term lists), 1 Lagrange table, 2 accumulate, 3 K / Z /
+ * compaction, 4 G1 points, 5 G2 points, 6 accumulate kernels only (device time
+ * between events); then two counts: 7 the accumulation's threads over all its
+ * rounds (each adds <= *acc_chunk items and writes one 32-B sum), 8 the terms;
+ * writes min(n, 9) values */
+int gg_groth16_setup_timings(gg_g16_setup_t h, double *ms, int n);
+int gg_groth16_setup_release(gg_g16_setup_t h);
+
 /* ------------------------------------------------------------ profiling
  * Kernel-level timing with HIP events recorded on the stream each kernel is
  * launched on (bench.py uses it for the roofline of the dominant kernel).
