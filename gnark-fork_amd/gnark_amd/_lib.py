@@ -28,6 +28,11 @@ GG_SETUP_CLASS_VK_K, GG_SETUP_CLASS_PK_K, GG_SETUP_CLASS_CK = 0, 1, 2
  GG_SETUP_DELTA1, GG_SETUP_BETA2, GG_SETUP_DELTA2, GG_SETUP_GAMMA2, GG_SETUP_VK_K, GG_SETUP_INFINITY_A,
  GG_SETUP_INFINITY_B, GG_SETUP_K_WIRE_INDEX, GG_SETUP_PEDERSEN_VK) = range(16)
 GG_SETUP_CK_BASIS, GG_SETUP_CK_BASIS_SIGMA = 0x100, 0x200
+# gg_plonk_setup_read parts
+(GG_PLONK_SETUP_QL, GG_PLONK_SETUP_QR, GG_PLONK_SETUP_QM, GG_PLONK_SETUP_QO, GG_PLONK_SETUP_QK, GG_PLONK_SETUP_S1,
+ GG_PLONK_SETUP_S2, GG_PLONK_SETUP_S3, GG_PLONK_SETUP_PERM, GG_PLONK_SETUP_LAGRANGE) = range(10)
+GG_PLONK_SETUP_QCP = 0x100
+GG_PLONK_SETUP_TIMING_SLOTS = 10
 
 
 # gg_exchange_fn (include/gnark_amd.h): all-to-all supplied by the caller
@@ -209,6 +214,15 @@ def _load():
         "gg_groth16_setup_read": ([P, I, P, S], I),
         "gg_groth16_setup_timings": ([P, ctypes.POINTER(ctypes.c_double), I], I),
         "gg_groth16_setup_release": ([P], I),
+        "gg_kzg_to_lagrange_g1": ([I, I, P, P, I, P, I, P], I),
+        "gg_plonk_setup_sizes": ([S, S, ctypes.POINTER(I), ctypes.POINTER(I)], I),
+        "gg_plonk_setup": ([I, S, S, S, P, P, P, S, I, P, P, P, P, P, P, S, P, PP], I),
+        "gg_plonk_setup_info": ([P, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I),
+                                 ctypes.POINTER(I)], I),
+        "gg_plonk_setup_read": ([P, I, P, S], I),
+        "gg_plonk_setup_timings": ([P, ctypes.POINTER(ctypes.c_double), I], I),
+        "gg_plonk_setup_pk": ([P, P, I, ctypes.POINTER(ctypes.c_int), PP], I),
+        "gg_plonk_setup_release": ([P], I),
         "gg_profile_enable": ([I], I),
         "gg_profile_get": ([ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),
                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)], I),
@@ -278,6 +292,8 @@ EXPORTED = [
     "gg_hint_supported", "gg_hint_eval_host", "gg_r1cs_set_hints", "gg_scs_set_hints",
     "gg_groth16_setup_layout", "gg_groth16_setup", "gg_groth16_setup_info", "gg_groth16_setup_read",
     "gg_groth16_setup_timings", "gg_groth16_setup_release",
+    "gg_kzg_to_lagrange_g1", "gg_plonk_setup_sizes", "gg_plonk_setup", "gg_plonk_setup_info", "gg_plonk_setup_read",
+    "gg_plonk_setup_timings", "gg_plonk_setup_pk", "gg_plonk_setup_release",
 ]
 
 

@@ -1,0 +1,41 @@
+"""KZG SRS helpers: the Lagrange form of a canonical SRS on the GPU
+(kzg.ToLagrangeG1, backend/plonk/bls12-381/setup.go:134) over the C ABI's
+gg_kzg_to_lagrange_g1 (csrc/ecntt.hip: an inverse DFT over G1 points)."""
+from __future__ import annotations
+
+from . import fr
+from ._lib import DeviceBuffer, GG_CURVE_BLS12_381, GG_CURVE_BN254, check, lib, ptr
+
+
+def _curve(curve: str):
+    if curve == "bls12-381":
+        return GG_CURVE_BLS12_381, 96, fr.bls_fr_mont, fr.bls_domain_generator
+    if curve == "bn254":
+        return GG_CURVE_BN254, 64, fr.fr_mont, fr.domain_generator
+    raise ValueError("curve must be 'bls12-381' or 'bn254'")
+
+
+def to_lagrange_g1(points, log_n: int, curve: str = "bls12-381", out_device: bool = False, omega: int = None,
+                   out=None):
+    """[L_i(tau)]G, i < n = 2^log_n, from points = [tau^j]G, j < n (affine, the
+    curve's layout; bytes or a DeviceBuffer).  out[i] = (1/n) sum_j omega^(-ij)
+    points[j] for any input points.  Returns bytes, or a DeviceBuffer with
+    out_device; `out` (a DeviceBuffer, possibly `points` itself) receives the
+    result in place of a new buffer.  omega: the domain's generator (default
+    gnark-crypto's fft.NewDomain choice)."""
+    cid, pt, mont, gen = _curve(curve)
+    if not 1 <= log_n <= 27:
+        raise ValueError("log_n must be in 1 .. 27")
+    w = mont(omega if omega is not None else gen(log_n))
+    nbytes = pt << log_n
+    in_dev = isinstance(points, DeviceBuffer)
+    if not in_dev:
+        points = bytes(points)
+        if len(points) < nbytes:
+            raise ValueError("need %d points of %d bytes" % (1 << log_n, pt))
+    if out is not None:
+        dst, out_device = out, True
+    else:
+        dst = DeviceBuffer(nbytes) if out_device else bytearray(nbytes)
+    check(lib.gg_kzg_to_lagrange_g1(cid, log_n, ptr(w), ptr(points), int(in_dev), ptr(dst), int(out_device), None))
+    return dst if out_device else bytes(dst)

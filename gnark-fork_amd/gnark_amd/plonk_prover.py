@@ -226,6 +226,30 @@ class ProvingKey:
         self.vk = VerifyingKey(n, self.omega, self.g, d[0:3], d[3], d[4], d[5], d[6], d[7], d[8:], nb_public,
                                list(commitment_indexes))
 
+    @classmethod
+    def from_handle(cls, handle, log_n: int, big_log: int, nb_public: int = 0,
+                    commitment_indexes: Sequence[int] = (), curve: str = "bls12-381") -> "ProvingKey":
+        """Wraps a gg_plonk_pk_t that the library built (gg_plonk_setup_pk): the
+        verifying key's digests are read back from the key (gg_plonk_pk_vk)."""
+        self = cls.__new__(cls)
+        F = self.field = _Field(curve)
+        self.curve = curve
+        self.log_n, self.n, self.big_log = log_n, 1 << log_n, big_log
+        self.omega = F.domain_generator(log_n)
+        self.omega_big = F.domain_generator(big_log)
+        self.g = F.gen
+        self.n_cmt = len(commitment_indexes)
+        self.nb_public = nb_public
+        self._reduce_cb = None
+        self.handle = handle
+        pt = F.pt
+        out = bytearray(pt * (8 + self.n_cmt))
+        check(lib.gg_plonk_pk_vk(handle, ptr(out), len(out)))
+        d = [bytes(out[pt * i:pt * (i + 1)]) for i in range(8 + self.n_cmt)]
+        self.vk = VerifyingKey(self.n, self.omega, self.g, d[0:3], d[3], d[4], d[5], d[6], d[7], d[8:], nb_public,
+                               list(commitment_indexes))
+        return self
+
     def devices(self) -> List[int]:
         """the key's device parts, primary first (gg_plonk_pk_devices)"""
         k = ctypes.c_int()
@@ -419,3 +443,123 @@ def proof_bytes(pr: Proof, curve: str = "bls12-381") -> bytes:
     return b"".join(pr.LRO + [pr.Z] + pr.H + pr.bsb22 + [pr.batched_H] +
                     [F.mont(v) for v in pr.claimed_values] + [pr.z_shifted_H, F.mont(pr.z_shifted_value)])
 
+
+
+# ---------------------------------------------------------------- Setup
+SETUP_PARTS = {"ql": 0, "qr": 1, "qm": 2, "qo": 3, "qk": 4, "s1": 5, "s2": 6, "s3": 7, "perm": 8, "lagrange": 9}
+SETUP_TIMINGS = ["validate_upload", "trace", "permutation", "s_gather", "inverse_ntts", "ecntt_stages",
+                 "ecntt_normalise", "total", "pk_host_bounce", "pk_build"]
+
+
+def setup_sizes(n_constraints: int, nb_public: int) -> Tuple[int, int]:
+    """(log_n, log_big) of initDomains (setup.go:275-290): the big domain is 8n
+    for sizeSystem = n_constraints + nb_public < 6 and 4n otherwise."""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    check(lib.gg_plonk_setup_sizes(n_constraints, nb_public, ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+class SetupData:
+    """plonk.Setup's results in HBM (gg_plonk_setup): the trace polynomials in
+    canonical regular form, the permutation and the Lagrange SRS.
+
+    wires / qidx: the arrays of gg_scs_create (uint32: xa, xb, xc per constraint;
+    qL, qR, qO, qM, qC ids per constraint); coeffs_mont: the coefficient table (fr
+    Montgomery bytes); commitments: per BSB22 commitment (committed constraint
+    indices, commitment constraint index) = (commitmentInfo[j].Committed,
+    .CommitmentIndex); kzg_g1: >= n + 3 canonical SRS points; kzg_lagrange_g1:
+    the n Lagrange points, or None to compute them on the GPU."""
+
+    def __init__(self, n_wires: int, nb_public: int, wires, qidx, coeffs_mont: bytes, kzg_g1, kzg_lagrange_g1=None,
+                 commitments: Sequence = (), curve: str = "bls12-381", omega: Optional[int] = None):
+        import numpy as np
+        F = self.field = _Field(curve)
+        self.curve = curve
+        wires = np.ascontiguousarray(wires, dtype=np.uint32)
+        qidx = np.ascontiguousarray(qidx, dtype=np.uint32)
+        n_cons = len(wires) // 3
+        self.nb_public = nb_public
+        self.commitment_indexes = [int(c[1]) for c in commitments]
+        off = np.zeros(len(commitments) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(c[0]) for c in commitments])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(c[0], dtype=np.uint32) for c in commitments])
+                                    if commitments else np.zeros(0, dtype=np.uint32), dtype=np.uint32)
+        idx = (ctypes.c_uint64 * max(1, len(commitments)))(*self.commitment_indexes)
+        if omega is None:
+            # fft.NewDomain(sizeSystem)'s generator; a size the library refuses is named by it below
+            omega = F.domain_generator(min(27, max(1, (max(n_cons + nb_public, 1) - 1).bit_length())))
+        kz = kzg_g1.to_host() if isinstance(kzg_g1, DeviceBuffer) else bytes(kzg_g1)
+        n_kzg = len(kz) // F.pt
+        kl = None if kzg_lagrange_g1 is None else bytes(kzg_lagrange_g1)
+        h = ctypes.c_void_p()
+        check(lib.gg_plonk_setup(F.cid, n_wires, n_cons, nb_public, ptr(wires), ptr(qidx), ptr(coeffs_mont),
+                                 len(coeffs_mont) // 32, len(commitments), ptr(off) if commitments else None,
+                                 ptr(flat) if commitments else None, idx if commitments else None,
+                                 ptr(F.mont(omega)), ptr(F.mont(F.gen)), ptr(kz), n_kzg, ptr(kl), ctypes.byref(h)))
+        self.handle = h
+        c, a, b, k, lc = (ctypes.c_int() for _ in range(5))
+        check(lib.gg_plonk_setup_info(h, ctypes.byref(c), ctypes.byref(a), ctypes.byref(b), ctypes.byref(k),
+                                      ctypes.byref(lc)))
+        self.log_n, self.log_big, self.n_cmt, self.lagrange_computed = a.value, b.value, k.value, bool(lc.value)
+        self.n = 1 << self.log_n
+
+    def read(self, part) -> bytes:
+        """part: 'ql', 'qr', 'qm', 'qo', 'qk', 's1', 's2', 's3' (canonical regular,
+        n fr), ('qcp', j), 'perm' (3n int64) or 'lagrange' (n points)."""
+        if isinstance(part, tuple):
+            which, size = 0x100 + int(part[1]), 32 * self.n
+        else:
+            which = SETUP_PARTS[part]
+            size = {"perm": 24 * self.n, "lagrange": self.field.pt * self.n}.get(part, 32 * self.n)
+        out = bytearray(size)
+        check(lib.gg_plonk_setup_read(self.handle, which, ptr(out), size))
+        return bytes(out)
+
+    def timings(self) -> dict:
+        """wall ms per phase (gg_plonk_setup_timings)"""
+        from ._lib import GG_PLONK_SETUP_TIMING_SLOTS as K
+        v = (ctypes.c_double * K)()
+        check(lib.gg_plonk_setup_timings(self.handle, v, K))
+        return dict(zip(SETUP_TIMINGS, list(v)))
+
+    def proving_key(self, devices: Optional[Sequence[int]] = None) -> ProvingKey:
+        """the device key of this setup (gg_plonk_setup_pk)"""
+        F = self.field
+        devs = list(devices) if devices is not None and len(devices) > 1 else []
+        h = ctypes.c_void_p()
+        check(lib.gg_plonk_setup_pk(self.handle, ptr(F.mont(F.domain_generator(self.log_big))), len(devs),
+                                    (ctypes.c_int * max(1, len(devs)))(*devs), ctypes.byref(h)))
+        return ProvingKey.from_handle(h, self.log_n, self.log_big, self.nb_public, self.commitment_indexes,
+                                      self.curve)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib.gg_plonk_setup_release(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def setup(system, kzg_g1, kzg_lagrange_g1=None, commitments: Sequence = (), devices: Optional[Sequence[int]] = None,
+          curve: Optional[str] = None, keep: bool = False):
+    """plonk.Setup (setup.go:108-171) on the GPU -> (ProvingKey, VerifyingKey).
+    system: a gnark_amd.solver.SparseR1CS, or the raw arrays (n_wires, nb_public,
+    wires, qidx, coeffs_mont) with curve=...; commitments as SetupData.  With
+    keep=True the SetupData comes back as a third value (read / timings)."""
+    if isinstance(system, (tuple, list)):
+        n_wires, nb_public, wires, qidx, coeffs = system
+        curve = curve or "bls12-381"
+    else:
+        n_wires, nb_public, wires, qidx, coeffs = (system.n_wires, system.nb_public, system.wires, system.qidx,
+                                                   system.coeffs_mont)
+        curve = curve or system.curve
+    sd = SetupData(n_wires, nb_public, wires, qidx, coeffs, kzg_g1, kzg_lagrange_g1, commitments, curve)
+    pk = sd.proving_key(devices)
+    if keep:
+        return pk, pk.vk, sd
+    sd.close()
+    return pk, pk.vk

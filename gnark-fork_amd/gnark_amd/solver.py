@@ -420,6 +420,7 @@ class SparseR1CS:
         lc = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint32) for x in levels])
                                   if levels else np.zeros(0, dtype=np.uint32), dtype=np.uint32)
         cbytes = b"".join(self._mont(int(k) % self.mod) for k in coeffs)
+        self.coeffs_mont = cbytes  # the coefficient table as uploaded (plonk_prover.setup reads it)
         h = ctypes.c_void_p()
         check(lib.gg_scs_create(cid, n_wires, self.n_constraints, nb_public, ptr(self.wires), ptr(self.qidx),
                                 ptr(self.flags), ptr(cbytes), len(coeffs), ptr(lo), ptr(lc), len(levels),

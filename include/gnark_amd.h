@@ -968,6 +968,91 @@ int gg_groth16_setup_read(gg_g16_setup_t h, int which, void *out_host, size_t by
 int gg_groth16_setup_timings(gg_g16_setup_t h, double *ms, int n);
 int gg_groth16_setup_release(gg_g16_setup_t h);
 
+/* ------------------------------------------------------------ PlonK Setup
+ * plonk.Setup (backend/plonk/bls12-381/setup.go:108-171, the same file under
+ * bn254/) on the GPU: from the sparse R1CS and the canonical KZG SRS to the
+ * trace polynomials, the permutation, the Lagrange SRS and the device key.
+ *
+ * The Lagrange SRS (kzg.ToLagrangeG1, setup.go:134) by an inverse DFT over G1
+ * points:  g1_out[i] = (1/n) sum_j omega^(-ij) g1_in[j], i in natural order,
+ * n = 2^log_n, 1 <= log_n <= 27; for g1_in[j] = [tau^j]G this is [L_i(tau)]G,
+ * the order of pk.KzgLagrange.G1.  Points: affine in the curve's layout
+ * (GG_CURVE_BN254 64 B, GG_CURVE_BLS12_381 96 B, Montgomery, infinity = (0, 0));
+ * g1_in and g1_out may alias; omega_mont: fr Montgomery, of exact order n.
+ * Affine coordinates are unique, so the result does not depend on the order of
+ * the butterflies.  GG_ERR_INVALID_ARG (before any device call): a null
+ * argument, log_n out of range, omega^(n/2) != -1, an unknown curve. */
+int gg_kzg_to_lagrange_g1(int curve, int log_n, const void *omega_mont, const void *g1_in, int in_on_device,
+                          void *g1_out, int out_on_device, void *hip_stream);
+
+typedef struct gg_plonk_setup *gg_plonk_setup_t;
+/* initDomains (setup.go:275-290), host only: sizeSystem = n_constraints +
+ * nb_public, n = 2^*log_n its next power of two, the big domain 2^*log_big = 8n
+ * when sizeSystem < 6 and 4n otherwise.  GG_ERR_INVALID_ARG: sizeSystem < 2
+ * (n < 2), log_n > 27. */
+int gg_plonk_setup_sizes(size_t n_constraints, size_t nb_public, int *log_n, int *log_big);
+/* Setup.  wires / qidx: the arrays of gg_scs_create (wires[3c..] = xa, xb, xc;
+ * qidx[5c..] = qL, qR, qO, qM, qC -- the trace's order is Ql, Qr, Qm, Qo, Qk);
+ * n_wires = NbInternalVariables + len(Public) + len(Secret); coeffs: n_coeffs
+ * fr Montgomery; committed[committed_off[j] .. committed_off[j + 1]) =
+ * commitmentInfo[j].Committed (constraint indices) and
+ * commitment_constraint_indexes[j] = commitmentInfo[j].CommitmentIndex, NULL
+ * arrays when n_cmt == 0; omega_mont / coset_shift_mont = Domain[0].Generator /
+ * FrMultiplicativeGen; kzg_g1 = srs.Pk.G1[:n_kzg], n_kzg >= n + 3 (setup.go:150);
+ * kzg_lagrange_g1 = the n points of pk.KzgLagrange.G1, or NULL to compute them
+ * here (gg_kzg_to_lagrange_g1 over kzg_g1[:n]).
+ *   trace (BuildTrace, setup.go:173-225): rows i < nb_public have ql = -1, row
+ *     nb_public + c the coefficients of constraint c, padding rows 0;
+ *     qcp_j[nb_public + k] = 1 for each committed k.
+ *   permutation (buildPermutation, setup.go:304-358): lro has 3n slots, the
+ *     unfilled ones (R and O of the public rows, the padding rows) hold wire 0;
+ *     perm[i] = the greatest j < i with lro[j] == lro[i], else the greatest j
+ *     with that wire (which may be i).
+ *   S1..S3 (computePermutationPolynomials, setup.go:363-407):
+ *     S_k[i] = ID[perm[k n + i]], ID[s] = u^(s div n) omega^(s mod n).
+ *   All 8 + n_cmt polynomials end in canonical regular form (setup.go:141-158).
+ * GG_ERR_INVALID_ARG, the message naming the offender, before any device call:
+ * n_wires == 0, a wire >= n_wires, a coefficient id >= n_coeffs, a committed
+ * index >= n_constraints, nb_public + a commitment index >= n, n_kzg < n + 3,
+ * n_cmt > 8, omega not of order n, everything gg_plonk_setup_sizes refuses. */
+int gg_plonk_setup(int curve, size_t n_wires, size_t n_constraints, size_t nb_public, const uint32_t *wires,
+                   const uint32_t *qidx, const void *coeffs, size_t n_coeffs, int n_cmt,
+                   const uint32_t *committed_off, const uint32_t *committed,
+                   const uint64_t *commitment_constraint_indexes, const void *omega_mont,
+                   const void *coset_shift_mont, const void *kzg_g1, size_t n_kzg, const void *kzg_lagrange_g1,
+                   gg_plonk_setup_t *out);
+/* all outputs nullable; *lagrange_computed = 1 when the Lagrange SRS was computed here */
+int gg_plonk_setup_info(gg_plonk_setup_t h, int *curve, int *log_n, int *log_big, int *n_cmt,
+                        int *lagrange_computed);
+/* parts for gg_plonk_setup_read */
+#define GG_PLONK_SETUP_QL 0 /* pk.trace.Ql canonical regular, n fr (setup.go:141-158); then Qr, Qm, Qo */
+#define GG_PLONK_SETUP_QR 1
+#define GG_PLONK_SETUP_QM 2
+#define GG_PLONK_SETUP_QO 3
+#define GG_PLONK_SETUP_QK 4 /* the incomplete Qk (completeQk, prove.go:397-423, adds the public inputs) */
+#define GG_PLONK_SETUP_S1 5 /* pk.trace.S1..S3 canonical regular */
+#define GG_PLONK_SETUP_S2 6
+#define GG_PLONK_SETUP_S3 7
+#define GG_PLONK_SETUP_PERM 8      /* pk.trace.S: 3n int64 */
+#define GG_PLONK_SETUP_LAGRANGE 9  /* pk.KzgLagrange.G1: n points */
+#define GG_PLONK_SETUP_QCP 0x100   /* + j: pk.trace.Qcp[j] canonical regular, n fr */
+/* copies part `which` to out_host; bytes must be the part's exact size */
+int gg_plonk_setup_read(gg_plonk_setup_t h, int which, void *out_host, size_t bytes);
+/* wall ms of the phases (each ended by a stream wait): 0 validation + upload,
+ * 1 trace, 2 permutation (sort + link), 3 S gather, 4 inverse NTTs, 5 EC-NTT
+ * stages, 6 EC-NTT normalisation (5, 6: device time between events, 0 when the
+ * caller brought the Lagrange SRS), 7 total; of the last gg_plonk_setup_pk:
+ * 8 the copy of the results to pinned host memory, 9 the key build; writes
+ * min(n, 10) values */
+int gg_plonk_setup_timings(gg_plonk_setup_t h, double *ms, int n);
+/* the device key of this setup (gg_plonk_pk_create_ex with vk_digests = NULL:
+ * the verifying key's digests are the key's own commitTrace, gg_plonk_pk_vk);
+ * omega_big_mont = Domain[1].Generator of 2^log_big (gg_plonk_setup_info);
+ * n_devices / devices as gg_plonk_pk_create_ex.  The setup stays valid. */
+int gg_plonk_setup_pk(gg_plonk_setup_t h, const void *omega_big_mont, int n_devices, const int *devices,
+                      gg_plonk_pk_t *out);
+int gg_plonk_setup_release(gg_plonk_setup_t h);
+
 /* ------------------------------------------------------------ profiling
  * Kernel-level timing with HIP events recorded on the stream each kernel is
  * launched on (bench.py uses it for the roofline of the dominant kernel).
