@@ -32,6 +32,10 @@ GG_SETUP_CK_BASIS, GG_SETUP_CK_BASIS_SIGMA = 0x100, 0x200
 (GG_PLONK_SETUP_QL, GG_PLONK_SETUP_QR, GG_PLONK_SETUP_QM, GG_PLONK_SETUP_QO, GG_PLONK_SETUP_QK, GG_PLONK_SETUP_S1,
  GG_PLONK_SETUP_S2, GG_PLONK_SETUP_S3, GG_PLONK_SETUP_PERM, GG_PLONK_SETUP_LAGRANGE) = range(10)
 GG_PLONK_SETUP_QCP = 0x100
+GG_VERIFY_OK, GG_VERIFY_SUBGROUP, GG_VERIFY_PEDERSEN, GG_VERIFY_PAIRING = 0, 1, 2, 3
+GG_POINT_OK, GG_POINT_NOT_ON_CURVE, GG_POINT_NOT_IN_SUBGROUP = 0, 1, 2
+GG_GT_BYTES = 384
+GG_VERIFY_MAX_K = 1024
 GG_PLONK_SETUP_TIMING_SLOTS = 10
 
 
@@ -223,6 +227,15 @@ def _load():
         "gg_plonk_setup_timings": ([P, ctypes.POINTER(ctypes.c_double), I], I),
         "gg_plonk_setup_pk": ([P, P, I, ctypes.POINTER(ctypes.c_int), PP], I),
         "gg_plonk_setup_release": ([P], I),
+        "gg_pairing_bn254": ([S, I, P, P, P], I),
+        "gg_pairing_check_bn254": ([S, I, P, P, P], I),
+        "gg_pairing_bn254_host": ([S, I, P, P, P], I),
+        "gg_g1_check_bn254": ([S, P, P], I),
+        "gg_g2_check_bn254": ([S, P, P], I),
+        "gg_hash_to_field_bn254": ([P, S, P, S, P], I),
+        "gg_groth16_vk_create": ([I, P, P, P, P, P, S, S, P, P, P, P, I, PP], I),
+        "gg_groth16_vk_destroy": ([P], I),
+        "gg_groth16_verify_batch": ([P, S, P, P, P, P, P], I),
         "gg_profile_enable": ([I], I),
         "gg_profile_get": ([ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),
                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)], I),
@@ -294,6 +307,8 @@ EXPORTED = [
     "gg_groth16_setup_timings", "gg_groth16_setup_release",
     "gg_kzg_to_lagrange_g1", "gg_plonk_setup_sizes", "gg_plonk_setup", "gg_plonk_setup_info", "gg_plonk_setup_read",
     "gg_plonk_setup_timings", "gg_plonk_setup_pk", "gg_plonk_setup_release",
+    "gg_pairing_bn254", "gg_pairing_check_bn254", "gg_pairing_bn254_host", "gg_g1_check_bn254", "gg_g2_check_bn254",
+    "gg_hash_to_field_bn254", "gg_groth16_vk_create", "gg_groth16_vk_destroy", "gg_groth16_verify_batch",
 ]
 
 

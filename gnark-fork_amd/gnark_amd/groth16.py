@@ -773,7 +773,7 @@ def prove_distributed_h(pk: ProvingKeyShard, hs: HShard, xchg: TorchExchange, so
 @dataclasses.dataclass
 class VerifyingKeyData:
     """Host copy of groth16.VerifyingKey (setup.go:63-82), gnark byte layouts.
-    e, deltaNeg and gammaNeg (vk.Precompute) are left to the verifier."""
+    e, deltaNeg and gammaNeg (vk.Precompute) are computed by the device key (VerifyingKey)."""
     alpha1: bytes
     beta1: bytes
     delta1: bytes
@@ -956,3 +956,96 @@ def setup_from_terms(nb_public: int, n_wires: int, constraints, **kw):
                 cids.append(index[k])
             off.append(len(wires))
     return setup(nb_public, n_wires, off, wires, cids, table or [1], **kw)
+
+
+# ------------------------------------------------------------------- Verify
+VERIFY_OK, VERIFY_SUBGROUP, VERIFY_PEDERSEN, VERIFY_PAIRING = 0, 1, 2, 3
+_VERIFY_MESSAGES = {
+    VERIFY_SUBGROUP: "points in the proof are not in the correct subgroup",   # verify.go:38
+    VERIFY_PEDERSEN: "failed to verify the commitments' proof of knowledge",  # pedersen Verify, verify.go:105
+    VERIFY_PAIRING: "pairing doesn't match",                                  # verify.go:37
+}
+
+
+class VerifyError(ValueError):
+    """groth16.Verify's error; .status is the GG_VERIFY_* value."""
+
+    def __init__(self, status: int):
+        super().__init__(_VERIFY_MESSAGES.get(status, f"verify status {status}"))
+        self.status = status
+
+
+class VerifyingKey:
+    """Device verifying key (gg_groth16_vk_create): the key's points, -gamma and
+    -delta, the fixed operands' line tables, e(alpha, beta)^m and the window
+    table of K[1:] stay in HBM for any number of verify_batch calls."""
+
+    def __init__(self, data: VerifyingKeyData):
+        self.data = data
+        curve = GG_CURVE_BN254 if data.curve == "bn254" else GG_CURVE_BLS12_381
+        g1b = _SIZES[data.curve][0]
+        committed = [list(c) for c in data.public_and_commitment_committed]
+        nc = len(committed)
+        self.n_commitments, self.nb_public = nc, data.nb_public
+        off = np.zeros(nc + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(c) for c in committed])
+        idx = np.ascontiguousarray([i for c in committed for i in c], dtype=np.uint32)
+        h = ctypes.c_void_p()
+        check(lib.gg_groth16_vk_create(
+            curve, ptr(data.alpha1), ptr(data.beta2), ptr(data.gamma2), ptr(data.delta2), ptr(data.K),
+            len(data.K) // g1b, data.nb_public, ptr(data.commitment_key_g) if nc else None,
+            ptr(data.commitment_key_g_root_sigma_neg) if nc else None, ptr(off) if nc else None,
+            ptr(idx) if len(idx) else None, nc, ctypes.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib.gg_groth16_vk_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _witness_bytes(w) -> bytes:
+    """fr Montgomery bytes of a public witness given as bytes or as integers."""
+    if isinstance(w, (bytes, bytearray, memoryview)):
+        return bytes(w)
+    if hasattr(w, "tobytes"):
+        return w.tobytes()
+    return b"".join(fr.fr_mont(int(x)) for x in w)
+
+
+def verify_batch(proofs: Sequence[Proof], vk: VerifyingKey, witnesses: Sequence) -> list:
+    """groth16.Verify of every (proof, public witness) pair under vk: a list of
+    VERIFY_* statuses, one deterministic verdict per proof.  A witness is the
+    public inputs without the ONE wire, as fr Montgomery bytes or as integers."""
+    n = len(proofs)
+    if n != len(witnesses):
+        raise ValueError(f"{n} proofs, {len(witnesses)} witnesses")
+    nc, nw = vk.n_commitments, vk.nb_public - 1
+    wb = [_witness_bytes(w) for w in witnesses]
+    for i, (p, w) in enumerate(zip(proofs, wb)):
+        if len(w) != 32 * nw:
+            raise ValueError(f"invalid witness size, got {len(w) // 32}, expected {nw} (public - ONE_WIRE)")
+        if len(p.Commitments) != nc:
+            raise ValueError(f"proof {i}: {len(p.Commitments)} commitments, the key has {nc}")
+    packed = b"".join(p.Ar + p.Bs + p.Krs for p in proofs)
+    cm = b"".join(b"".join(p.Commitments) for p in proofs)
+    pok = b"".join(p.CommitmentPok for p in proofs)
+    wit = b"".join(wb)
+    status = bytearray(n)
+    check(lib.gg_groth16_verify_batch(vk.handle, n, ptr(packed), ptr(cm) if nc else None, ptr(pok) if nc else None,
+                                      ptr(wit) if nw else None, ptr(status)))
+    return list(status)
+
+
+def verify(proof: Proof, vk: VerifyingKey, public_witness) -> None:
+    """groth16.Verify (verify.go:43-140): returns None for a valid proof, raises
+    VerifyError with gnark's message otherwise."""
+    st = verify_batch([proof], vk, [public_witness])[0]
+    if st != VERIFY_OK:
+        raise VerifyError(st)

@@ -1053,6 +1053,88 @@ int gg_plonk_setup_pk(gg_plonk_setup_t h, const void *omega_big_mont, int n_devi
                       gg_plonk_pk_t *out);
 int gg_plonk_setup_release(gg_plonk_setup_t h);
 
+/* ------------------------------------------------- pairing, Groth16 Verify
+ * BN254 optimal ate pairing and groth16.Verify (backend/groth16/bn254/
+ * verify.go:43-140) for batches of proofs under one verifying key.
+ *
+ * A GT element is gnark-crypto's E12 in memory: C0.B0, C0.B1, C0.B2, C1.B0,
+ * C1.B1, C1.B2, each an E2 {A0, A1} in Montgomery form, 384 B.  Every pairing
+ * value is e(P, Q)^m for the fixed m = 2x(6x^2 + 3x + 1), x = 4965661367192848881
+ * (gcd(m, r) = 1; gnark_amd.pairing.GT_MULTIPLE): products, comparisons and
+ * the check "= 1" are those of the reduced pairing.  A G1 or G2 operand of all
+ * zero bytes is the infinity and contributes the factor 1. */
+#define GG_GT_BYTES 384
+/* out[i] = prod_{j<k} e(g1[i k + j], g2[i k + j]), i < n: n GT values
+ * (curve.Pair / curve.MillerLoop + FinalExponentiation, verify.go:71, 124,
+ * 134).  g1: n k G1Affine, g2: n k G2Affine, gt_out: n x 384 B; each pointer
+ * may be a host or a device pointer (found by hipPointerGetAttributes, after
+ * the argument checks).  The operands are NOT checked for membership:
+ * gg_g1_check_bn254 / gg_g2_check_bn254. */
+int gg_pairing_bn254(size_t n, int k, const void *g1, const void *g2, void *gt_out);
+/* the same products, ok_out[i] (uint8) = 1 iff product i is 1 (curve.PairingCheck,
+ * pedersen VerifyingKey.Verify as called at verify.go:105) */
+int gg_pairing_check_bn254(size_t n, int k, const void *g1, const void *g2, uint8_t *ok_out);
+/* the same templates on the calling host thread (no device call; host
+ * pointers): for small n, and the check of the tower where there is no GPU */
+int gg_pairing_bn254_host(size_t n, int k, const void *g1, const void *g2, void *gt_out);
+/* flags_out[i] (uint8) for n points, host or device pointers: 0 good (the
+ * infinity included), 1 not on the curve, 2 on the curve but not in the
+ * subgroup of order r (proof.isValid, verify.go:61: Ar, Krs IsInSubGroup --
+ * G1 has cofactor 1, so 2 never occurs there -- and Bs IsInSubGroup) */
+#define GG_POINT_OK 0
+#define GG_POINT_NOT_ON_CURVE 1
+#define GG_POINT_NOT_IN_SUBGROUP 2
+int gg_g1_check_bn254(size_t n, const void *g1, uint8_t *flags_out);
+int gg_g2_check_bn254(size_t n, const void *g2, uint8_t *flags_out);
+/* fr.Hash(msg, dst, 1) on the host (hash_to_field.New(dst), verify.go:49, 89-97):
+ * 48 B of RFC 9380 expand_message_xmd over SHA-256, big-endian, mod r; out32 =
+ * one fr in Montgomery form.  msg may be NULL when len == 0; dst_len <= 255. */
+int gg_hash_to_field_bn254(const void *msg, size_t len, const void *dst, size_t dst_len, void *out32);
+
+typedef struct gg_groth16_vk *gg_groth16_vk_t;
+/* largest len(vk.G1.K) of a device verifying key: the public-input sum reads a
+ * table of 32 x 256 multiples (512 KiB) per point of K[1:] */
+#define GG_VERIFY_MAX_K 1024
+/* The device verifying key (groth16.VerifyingKey, setup.go:63-82, with
+ * vk.Precompute, verify.go / setup.go:  e = e(alpha, beta), deltaNeg, gammaNeg).
+ * Host pointers: alpha1 G1Affine; beta2, gamma2, delta2 G2Affine; K = vk.G1.K,
+ * n_K points, n_K = nb_public + n_commitments (nb_public counts the ONE wire);
+ * ped_g / ped_g_root_sigma_neg = vk.CommitmentKey.G / .GRootSigmaNeg (G2Affine)
+ * and committed_idx[committed_off[j] .. committed_off[j + 1]) =
+ * vk.PublicAndCommitmentCommitted[j] (public-witness indexes counted with the
+ * ONE wire, so 1 <= index < nb_public + j), all four NULL when
+ * n_commitments == 0.  Uploads the key, negates gamma and delta, precomputes
+ * the line coefficients of -delta, -gamma, G and GRootSigmaNeg, e(alpha, beta)^m
+ * and the window table of K[1:].
+ * GG_ERR_INVALID_ARG before any device call, the message naming the offender: a
+ * null pointer, nb_public == 0, n_K != nb_public + n_commitments,
+ * n_K > GG_VERIFY_MAX_K, n_commitments < 0, a committed index out of range, a
+ * G2 point of the key at infinity.  GG_ERR_UNSUPPORTED: curve != GG_CURVE_BN254. */
+int gg_groth16_vk_create(int curve, const void *alpha1, const void *beta2, const void *gamma2, const void *delta2,
+                         const void *K, size_t n_K, size_t nb_public, const void *ped_g,
+                         const void *ped_g_root_sigma_neg, const uint32_t *committed_off,
+                         const uint32_t *committed_idx, int n_commitments, gg_groth16_vk_t *out);
+int gg_groth16_vk_destroy(gg_groth16_vk_t vk);
+/* status of one proof, in the order verify.go decides them */
+#define GG_VERIFY_OK 0
+#define GG_VERIFY_SUBGROUP 1 /* verify.go:61 errCorrectSubgroupCheckFailed; also a commitment or PoK off the curve */
+#define GG_VERIFY_PEDERSEN 2 /* verify.go:105 the commitments' proof of knowledge */
+#define GG_VERIFY_PAIRING 3  /* verify.go:135 errPairingCheckFailed */
+/* groth16.Verify of n proofs under one key; every proof gets its own verdict.
+ * proofs: n x 256 B (Ar G1Affine | Bs G2Affine | Krs G1Affine); commitments:
+ * n x n_commitments G1Affine; poks: n G1Affine (proof.CommitmentPok) -- both
+ * NULL without commitments; public_witness: n x (nb_public - 1) fr Montgomery,
+ * without the ONE wire (NULL when nb_public == 1); status_out: n uint8.  Host or
+ * device pointers.  The commitment hashes (verify.go:82-100) and the folding
+ * challenge run on the host, everything else on the device: the point checks,
+ * the folded commitment, kSum = K[0] + sum x_i K[i + 1] + sum C_j
+ * (verify.go:110-119), the Pedersen check and
+ * e(Krs, -delta) e(Ar, Bs) e(kSum, -gamma) == e (verify.go:71, 124, 134-135).
+ * Returns GG_OK whenever the batch ran, whatever the verdicts;
+ * GG_ERR_INVALID_ARG (before any device call): vk NULL, n == 0, a null array. */
+int gg_groth16_verify_batch(gg_groth16_vk_t vk, size_t n, const void *proofs, const void *commitments,
+                            const void *poks, const void *public_witness, uint8_t *status_out);
+
 /* ------------------------------------------------------------ profiling
  * Kernel-level timing with HIP events recorded on the stream each kernel is
  * launched on (bench.py uses it for the roofline of the dominant kernel).
