@@ -107,6 +107,17 @@ struct DevBuf {
     }
 };
 
+// b <- a copy of the host array src (at least 16 bytes, so b.p is never null)
+inline void upload(DevBuf& b, const void* src, size_t bytes) {
+    b.alloc(bytes > 16 ? bytes : 16);
+    if (bytes) GG_HIP(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
+}
+// the same on stream st: src must stay as it is until the caller has waited for st
+inline void upload(DevBuf& b, const void* src, size_t bytes, hipStream_t st) {
+    b.alloc(bytes > 16 ? bytes : 16);
+    if (bytes) GG_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
+}
+
 // bump allocator over one device buffer: per-task scratch that is reused across
 // calls (no hipMalloc / hipFree -- which synchronise the device -- inside a
 // prove).  get() hands out 256-B aligned slices; reset() recycles them all.

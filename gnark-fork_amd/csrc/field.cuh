@@ -415,6 +415,38 @@ using Fr = Fe<FrCfg>;
 using FpBls = Fe<FpBlsCfg>;
 using FrBls = Fe<FrBlsCfg>;
 
+// 32-byte field elements in global memory: two 16-byte accesses
+template <class F>
+__device__ __forceinline__ F ld_fr(const F* p) {
+    static_assert(sizeof(F) == 32, "8-limb scalar field");
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+    uint4 a = q[0], b = q[1];
+    F r;
+    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
+    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
+    return r;
+}
+template <class F>
+__device__ __forceinline__ void st_fr(F* p, const F& r) {
+    uint4* q = reinterpret_cast<uint4*>(p);
+    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
+    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
+}
+// A read around the (write-through, non-coherent) L1, for a thread that reads
+// values stored earlier in the same launch (the solvers' strand kernels)
+template <class F>
+__device__ __forceinline__ F ld_fr_l2(const F* p) {
+    const uint64_t* q = reinterpret_cast<const uint64_t*>(p);
+    F r;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint64_t x = __hip_atomic_load(q + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        r.v[2 * k] = (uint32_t)x;
+        r.v[2 * k + 1] = (uint32_t)(x >> 32);
+    }
+    return r;
+}
+
 // ---------------------------------------------------------------------------
 // Fp2 = Fp[u] / (u^2 + 1)   (gnark-crypto bn254 E2 layout: {A0, A1})
 // ---------------------------------------------------------------------------

@@ -72,22 +72,6 @@ struct WipeBuf : DevBuf {
     ~WipeBuf() { wipe(); }
 };
 
-template <class F>
-__device__ __forceinline__ F ldfr(const F* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    uint4 a = q[0], b = q[1];
-    F r;
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-    return r;
-}
-template <class F>
-__device__ __forceinline__ void stfr(F* p, const F& r) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
-
 // ---------------------------------------------------------------- uint32 scan
 // out[i] = sum of in[0..i) for i < m (in place allowed: a thread reads its own
 // items before it writes them); bsum[b] = the total of block b
@@ -208,32 +192,32 @@ __global__ void __launch_bounds__(ACC_BLOCK) k_acc(const uint32_t* prev_off, con
     for (uint32_t e = 0; e < m; e++) {
         if (FIRST) {
             const uint2 en = ent[base + e];
-            acc = acc + ldfr(coef + en.y) * ldfr(L + en.x);
+            acc = acc + ld_fr(coef + en.y) * ld_fr(L + en.x);
         } else {
-            acc = acc + ldfr(psrc + base + e);
+            acc = acc + ld_fr(psrc + base + e);
         }
     }
-    if (work == 1u) stfr(out + k, acc);
-    else stfr(pdst + i, acc);
+    if (work == 1u) st_fr(out + k, acc);
+    else st_fr(pdst + i, acc);
 }
 
 // ---------------------------------------------------------------- scalars
 template <class F>
 __global__ void __launch_bounds__(256) k_fill_geo(F* x, size_t n, F first, F ratio) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) stfr(x + i, i ? ratio : first);
+    if (i < n) st_fr(x + i, i ? ratio : first);
 }
 // den[j] = tau - w^j
 template <class F>
 __global__ void __launch_bounds__(256) k_den(const F* wj, F* den, size_t n, F tau) {
     const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) stfr(den + j, tau - ldfr(wj + j));
+    if (j < n) st_fr(den + j, tau - ld_fr(wj + j));
 }
 // L[j] = c * w^j / (tau - w^j), in place over the inverted denominators
 template <class F>
 __global__ void __launch_bounds__(256) k_lagrange(const F* wj, F* L, size_t n, F c) {
     const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) stfr(L + j, c * ldfr(wj + j) * ldfr(L + j));
+    if (j < n) st_fr(L + j, c * ld_fr(wj + j) * ld_fr(L + j));
 }
 // pk.G1.Z scalars: zs[r] = z[brev(r)] for r < n - 1 (setup.go:265-267 on scalars)
 template <class F>
@@ -241,7 +225,7 @@ __global__ void __launch_bounds__(256) k_z_brev(const F* z, F* zs, uint32_t n, i
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t r = log_n ? (__brev(i) >> (32 - log_n)) : 0u;
-    if (r + 1u < n) stfr(zs + r, ldfr(z + i));
+    if (r + 1u < n) st_fr(zs + r, ld_fr(z + i));
 }
 // K of wire w into its class slot; infinity flags by value; keep flags for the compaction
 template <class F>
@@ -264,7 +248,7 @@ __global__ void __launch_bounds__(256) k_key_scalars(KParams<F> P) {
         P.keep_b[w] = 0;
         return;
     }
-    const F a = ldfr(P.abc + w), b = ldfr(P.abc + (size_t)P.nw + w), c = ldfr(P.abc + 2 * (size_t)P.nw + w);
+    const F a = ld_fr(P.abc + w), b = ld_fr(P.abc + (size_t)P.nw + w), c = ld_fr(P.abc + 2 * (size_t)P.nw + w);
     const bool za = a.is_zero(), zb = b.is_zero();
     P.inf_a[w] = za;
     P.inf_b[w] = zb;
@@ -273,14 +257,14 @@ __global__ void __launch_bounds__(256) k_key_scalars(KParams<F> P) {
     const F t = P.beta * a + P.alpha * b + c;
     const uint32_t cl = P.cls[w], s = P.slot[w];
     if (cl == GG_SETUP_CLASS_PK_K) {
-        stfr(P.pk_k + s, t * P.delta_inv);
+        st_fr(P.pk_k + s, t * P.delta_inv);
     } else {
         const F k = t * P.gamma_inv;
         if (cl == GG_SETUP_CLASS_VK_K) {
-            stfr(P.vk_k + s, k);
+            st_fr(P.vk_k + s, k);
         } else {
-            stfr(P.ck_k + s, k);
-            stfr(P.ck_sigma + s, k * P.sigma);
+            st_fr(P.ck_k + s, k);
+            st_fr(P.ck_sigma + s, k * P.sigma);
         }
     }
 }
@@ -288,7 +272,7 @@ template <class F>
 __global__ void __launch_bounds__(256) k_compact(const F* in, const uint32_t* pos, uint32_t nw, F* out) {
     const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= nw) return;
-    if (pos[w + 1] != pos[w]) stfr(out + pos[w], ldfr(in + w));
+    if (pos[w + 1] != pos[w]) st_fr(out + pos[w], ld_fr(in + w));
 }
 
 // ---------------------------------------------------------------- host
@@ -477,10 +461,6 @@ void run_setup(const SetupArgs& a, gg_g16_setup* h) {
     }
 
     std::vector<std::unique_ptr<DevBuf>> tmp;  // scan scratch (counts only)
-    auto up = [&](DevBuf& b, const void* src, size_t bytes) {
-        b.alloc(std::max<size_t>(bytes, 16));
-        if (bytes) GG_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
-    };
     auto zero = [&](DevBuf& b) { GG_HIP(hipMemsetAsync(b.p, 0, b.bytes, st)); };
     auto u32 = [](DevBuf& b) { return b.as<uint32_t>(); };
     auto rd32 = [&](const uint32_t* p) {
@@ -492,12 +472,12 @@ void run_setup(const SetupArgs& a, gg_g16_setup* h) {
 
     // ---- 2. transposed system
     DevBuf d_off, d_wire, d_cidx, d_coef, d_cls, d_slot;
-    up(d_off, a.off, (nrows + 1) * 4);
-    up(d_wire, a.wire, nterms * 4);
-    up(d_cidx, a.cidx, nterms * 4);
-    up(d_coef, a.coeffs, a.ncoef * 32);
-    up(d_cls, lay.cls.data(), a.nw * 4);
-    up(d_slot, lay.slot.data(), a.nw * 4);
+    upload(d_off, a.off, (nrows + 1) * 4, st);
+    upload(d_wire, a.wire, nterms * 4, st);
+    upload(d_cidx, a.cidx, nterms * 4, st);
+    upload(d_coef, a.coeffs, a.ncoef * 32, st);
+    upload(d_cls, lay.cls.data(), a.nw * 4, st);
+    upload(d_slot, lay.slot.data(), a.nw * 4, st);
     DevBuf cnt((nk + 1) * 4), list_off((nk + 1) * 4), cursor(nk * 4), ent(std::max<size_t>(nterms, 1) * 8);
     zero(cnt);
     zero(cursor);

@@ -245,16 +245,6 @@ struct HintDev {
     uint32_t* fail;
 };
 
-template <class C>
-__device__ __forceinline__ Fe<C> hint_ld(const Fe<C>* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    Fe<C> r;
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-    return r;
-}
-
 // positions [first, first + count) of lvl_hints: one level's hints
 template <class C>
 __global__ void __launch_bounds__(256) k_hint_eval(HintDev<C> d, uint32_t first, uint32_t count) {
@@ -270,14 +260,14 @@ __global__ void __launch_bounds__(256) k_hint_eval(HintDev<C> d, uint32_t first,
         for (uint32_t t = d.expr_off[e], te = d.expr_off[e + 1]; t < te; t++) {
             const uint32_t w = d.term_wire[t], k = d.term_coeff[t];
             if (w == HINT_CONST_WIRE) {
-                acc = acc + hint_ld(d.coef + k);
+                acc = acc + ld_fr(d.coef + k);
                 continue;
             }
             if (!d.solved[w]) {
                 unsolved = true;
                 continue;
             }
-            acc = acc + (k == d.one_idx ? hint_ld(d.W + w) : hint_ld(d.coef + k) * hint_ld(d.W + w));
+            acc = acc + (k == d.one_idx ? ld_fr(d.W + w) : ld_fr(d.coef + k) * ld_fr(d.W + w));
         }
         if (e == e0) x0 = acc;
         else x1 = acc;
@@ -285,9 +275,8 @@ __global__ void __launch_bounds__(256) k_hint_eval(HintDev<C> d, uint32_t first,
     uint32_t* out = d.packed + 16 * (size_t)pos;
     if (unsolved) {  // the levels do not match the system
         atomicMin(d.fail + 1, HINT_FAIL_BIT | h);
-        uint4* q = reinterpret_cast<uint4*>(out);
-#pragma unroll
-        for (int k = 0; k < 4; k++) q[k] = make_uint4(0, 0, 0, 0);
+        st_fr(reinterpret_cast<F*>(out), F::zero());
+        st_fr(reinterpret_cast<F*>(out) + 1, F::zero());
     } else {
         hint_eval<C>(d.kind[h], x0, x1, out);
     }
@@ -311,11 +300,9 @@ __global__ void __launch_bounds__(256) k_hint_scatter(HintDev<C> d, uint32_t fir
     }
     const uint32_t pos = first + lo, h = d.lvl_hints[pos], j = target - pref[lo], kind = d.kind[h];
     const uint32_t* pk = d.packed + 16 * (size_t)pos;
-    const F v = hint_is_field(kind) ? hint_ld(reinterpret_cast<const F*>(pk)) : hint_const<C>(hint_digit(kind, pk, j));
+    const F v = hint_is_field(kind) ? ld_fr(reinterpret_cast<const F*>(pk)) : hint_const<C>(hint_digit(kind, pk, j));
     const uint32_t w = d.out_start[h] + j;
-    uint4* q = reinterpret_cast<uint4*>(d.W + w);
-    q[0] = make_uint4(v.v[0], v.v[1], v.v[2], v.v[3]);
-    q[1] = make_uint4(v.v[4], v.v[5], v.v[6], v.v[7]);
+    st_fr(d.W + w, v);
     d.solved[w] = 1;
 }
 
@@ -415,19 +402,15 @@ struct HintSet {
                 pf[i + 1] = pf[i] + (h_out_end[h] - h_out_start[h]);
             }
         }
-        auto up = [](DevBuf& b, const void* src, size_t bytes) {
-            b.alloc(std::max<size_t>(bytes, 16));
-            if (bytes) GG_HIP(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-        };
         if (n_hints) {
-            up(kind, kinds.data(), n_hints * 4);
-            up(in_off, h_in_off, (n_hints + 1) * 4);
-            up(expr_off, h_expr_off, (n_expr + 1) * 4);
-            up(term_wire, h_term_wire, n_terms * 4);
-            up(term_coeff, h_term_coeff, n_terms * 4);
-            up(out_start, h_out_start, n_hints * 4);
-            up(lvl_hints, h_level_hints, n_hints * 4);
-            up(lvl_pref, pf.data(), (n_hints + 1) * 4);
+            upload(kind, kinds.data(), n_hints * 4);
+            upload(in_off, h_in_off, (n_hints + 1) * 4);
+            upload(expr_off, h_expr_off, (n_expr + 1) * 4);
+            upload(term_wire, h_term_wire, n_terms * 4);
+            upload(term_coeff, h_term_coeff, n_terms * 4);
+            upload(out_start, h_out_start, n_hints * 4);
+            upload(lvl_hints, h_level_hints, n_hints * 4);
+            upload(lvl_pref, pf.data(), (n_hints + 1) * 4);
             packed.alloc(n_hints * 64);
         }
         level_off.assign(h_level_off, h_level_off + n_levels + 1);

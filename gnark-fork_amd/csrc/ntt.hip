@@ -156,28 +156,10 @@ __device__ __forceinline__ uint32_t brev_bits(uint32_t i, int L) {
 }
 
 template <class F>
-__device__ __forceinline__ F load_fr(const F* p) {
-    static_assert(sizeof(F) == 32, "8-limb scalar field");
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    uint4 a = q[0], b = q[1];
-    F r;
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-    return r;
-}
-
-template <class F>
-__device__ __forceinline__ void store_fr(F* p, const F& r) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
-
-template <class F>
 __device__ __forceinline__ F apply_scale(const ScaleSpec<F>& s, uint32_t g, int L, const F& x) {
     uint32_t e = s.bitrev ? brev_bits(g, L) : g;
-    F f = load_fr(s.hi + (e >> s.shift));
-    if (s.lo) f = f * load_fr(s.lo + (e & ((1u << s.shift) - 1)));
+    F f = ld_fr(s.hi + (e >> s.shift));
+    if (s.lo) f = f * ld_fr(s.lo + (e & ((1u << s.shift) - 1)));
     return x * f;
 }
 
@@ -205,7 +187,7 @@ __device__ __forceinline__ void ntt_round(const PassParams<F>& P, uint32_t* lds,
         if (first) {
 #pragma unroll
             for (int m = 0; m < R; m++) {
-                x[m] = load_fr(P.in + g[m]);
+                x[m] = ld_fr(P.in + g[m]);
                 if (P.has_pre) x[m] = apply_scale(P.pre, g[m], P.log_n, x[m]);
             }
         } else {
@@ -228,24 +210,24 @@ __device__ __forceinline__ void ntt_round(const PassParams<F>& P, uint32_t* lds,
                 const uint32_t i = g[m] & bmask;
                 if constexpr (NttLazy<F>::on) {
                     if (DIT) {
-                        F t = i ? mul_nored(x[m2], load_fr(twb + i)) : x[m2];
+                        F t = i ? mul_nored(x[m2], ld_fr(twb + i)) : x[m2];
                         x[m2] = sub2p(x[m], t);
                         x[m] = add2p(x[m], t);
                     } else {
                         F d = subnr2p(x[m], x[m2]);
                         x[m] = add2p(x[m], x[m2]);
-                        x[m2] = i ? mul_nored(d, load_fr(twb + i)) : red2p(d);
+                        x[m2] = i ? mul_nored(d, ld_fr(twb + i)) : red2p(d);
                     }
                     continue;
                 }
                 if (DIT) {
-                    F t = i ? x[m2] * load_fr(twb + i) : x[m2];
+                    F t = i ? x[m2] * ld_fr(twb + i) : x[m2];
                     x[m2] = x[m] - t;
                     x[m] = x[m] + t;
                 } else {
                     F d = x[m] - x[m2];
                     x[m] = x[m] + x[m2];
-                    x[m2] = i ? d * load_fr(twb + i) : d;
+                    x[m2] = i ? d * ld_fr(twb + i) : d;
                 }
             }
         }
@@ -256,10 +238,10 @@ __device__ __forceinline__ void ntt_round(const PassParams<F>& P, uint32_t* lds,
                 // lazy fields: the post-scale's full product also brings y < 2r below r
                 if (NttLazy<F>::on && P.canon_out && !P.has_post) y = canon(y);
                 if (P.has_post) y = apply_scale(P.post, g[m], P.log_n, y);
-                if (P.epi_mul_sub) y = load_fr(P.ea + g[m]) * load_fr(P.eb + g[m]) - y;
-                if (P.epi_mul) y = load_fr(P.ea + g[m]) * y;
-                if (P.epi_sub) y = y - load_fr(P.ea + g[m]);
-                store_fr(P.out + g[m], y);
+                if (P.epi_mul_sub) y = ld_fr(P.ea + g[m]) * ld_fr(P.eb + g[m]) - y;
+                if (P.epi_mul) y = ld_fr(P.ea + g[m]) * y;
+                if (P.epi_sub) y = y - ld_fr(P.ea + g[m]);
+                st_fr(P.out + g[m], y);
             }
         } else {
 #pragma unroll
@@ -293,13 +275,13 @@ __global__ void __launch_bounds__(kNttThreads<MAXNB>, kNttWaves<MAXNB>) k_ntt_pa
     if (k == 0) {  // n = 1: scaling only
         for (int e = threadIdx.x; e < T; e += blockDim.x) {
             uint32_t g = base_hi | (lo0 + (uint32_t)e);
-            F x = load_fr(P.in + g);
+            F x = ld_fr(P.in + g);
             if (P.has_pre) x = apply_scale(P.pre, g, P.log_n, x);
             if (P.has_post) x = apply_scale(P.post, g, P.log_n, x);
-            if (P.epi_mul_sub) x = load_fr(P.ea + g) * load_fr(P.eb + g) - x;
-            if (P.epi_mul) x = load_fr(P.ea + g) * x;
-            if (P.epi_sub) x = x - load_fr(P.ea + g);
-            store_fr(P.out + g, x);
+            if (P.epi_mul_sub) x = ld_fr(P.ea + g) * ld_fr(P.eb + g) - x;
+            if (P.epi_mul) x = ld_fr(P.ea + g) * x;
+            if (P.epi_sub) x = x - ld_fr(P.ea + g);
+            st_fr(P.out + g, x);
         }
         return;
     }
@@ -342,8 +324,8 @@ __global__ void k_stage_twiddles(F* out, size_t count, int L, const F* hi, const
     int b = 31 - __clz((int)v);
     uint32_t i = v - (1u << b);
     uint32_t ex = i << (L - 1 - b);
-    F x = load_fr(hi + (ex >> S)) * load_fr(lo + (ex & ((1u << S) - 1)));
-    store_fr(out + t, x);
+    F x = ld_fr(hi + (ex >> S)) * ld_fr(lo + (ex & ((1u << S) - 1)));
+    st_fr(out + t, x);
 }
 
 
@@ -806,7 +788,7 @@ struct PowTab {
     const F *hi, *lo;
     int S;
     __device__ __forceinline__ F at(uint32_t e) const {
-        return load_fr(hi + (e >> S)) * load_fr(lo + (e & ((1u << S) - 1)));
+        return ld_fr(hi + (e >> S)) * ld_fr(lo + (e & ((1u << S) - 1)));
     }
 };
 
@@ -854,8 +836,8 @@ __global__ void k_gather_cyclic(F* y, const F* x, size_t len, size_t m, int rank
     size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= m) return;
     size_t i = (size_t)rank + (size_t)N * j;
-    F v = i < len ? load_fr(x + i) : F::zero();
-    store_fr(y + j, v);
+    F v = i < len ? ld_fr(x + i) : F::zero();
+    st_fr(y + j, v);
 }
 
 // send[(r * npoly + poly) * chunk + q] = y[p] * w^(sign * rank * bitrev_M(p)), p = r chunk + q
@@ -865,10 +847,10 @@ __global__ void k_twist_scatter(F* send, const F* y, size_t m, size_t chunk, int
     size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= m) return;
     uint32_t c1 = brev_bits((uint32_t)p, M);
-    F v = load_fr(y + p);
+    F v = ld_fr(y + p);
     if (rank) v = v * tw.at(rank * c1);
     size_t r = p / chunk, q = p - r * chunk;
-    store_fr(send + (r * npoly + poly) * chunk + q, v);
+    st_fr(send + (r * npoly + poly) * chunk + q, v);
 }
 
 // phase 2: finish the inverse transform (size-N iDFT, 1/N), scale by g^c, start
@@ -890,11 +872,11 @@ __global__ void __launch_bounds__(256) k_cross_fwd(F* send, const F* recv, size_
     // out[k2] = DFT_N(co)[k2] * w^(c1 k2) = g^c1 w^(c1 k2) * DFT_N(iDFT_N(in) * cs)[k2]
     F x[N];
 #pragma unroll
-    for (int k = 0; k < N; k++) x[k] = load_fr(recv + ((size_t)k * 3 + poly) * chunk + q);
+    for (int k = 0; k < N; k++) x[k] = ld_fr(recv + ((size_t)k * 3 + poly) * chunk + q);
     dft_small<F, N>(x, R.inv);
     if (poly == 2) {
 #pragma unroll
-        for (int c2 = 0; c2 < N; c2++) store_fr(ccoef + (size_t)c2 * chunk + q, x[c2] * cden);
+        for (int c2 = 0; c2 < N; c2++) st_fr(ccoef + (size_t)c2 * chunk + q, x[c2] * cden);
         return;
     }
 #pragma unroll
@@ -905,7 +887,7 @@ __global__ void __launch_bounds__(256) k_cross_fwd(F* send, const F* recv, size_
 #pragma unroll
     for (int k2 = 0; k2 < N; k2++) {
         if (k2) f = f * wc;
-        store_fr(send + ((size_t)k2 * 2 + poly) * chunk + q, x[k2] * f);
+        st_fr(send + ((size_t)k2 * 2 + poly) * chunk + q, x[k2] * f);
     }
 }
 
@@ -915,7 +897,7 @@ __global__ void k_unpack(F* y, const F* recv, size_t m, size_t chunk, int npoly,
     size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= m) return;
     size_t r = p / chunk, q = p - r * chunk;
-    store_fr(y + p, load_fr(recv + (r * npoly + poly) * chunk + q));
+    st_fr(y + p, ld_fr(recv + (r * npoly + poly) * chunk + q));
 }
 
 // phase 4: size-N iDFT * den / N * g^-c, written at N q + bitrev_N(c2)
@@ -929,13 +911,13 @@ __global__ void __launch_bounds__(256) k_cross_inv_out(F* h, const F* recv, size
     // iDFT_N(in)[c2] * scale * g^-(c1 + m c2) = g^-c1 * (iDFT_N(in)[c2] * cs[c2])
     F x[N];
 #pragma unroll
-    for (int k = 0; k < N; k++) x[k] = load_fr(recv + (size_t)k * chunk + q);
+    for (int k = 0; k < N; k++) x[k] = ld_fr(recv + (size_t)k * chunk + q);
     dft_small<F, N>(x, R.inv);
     const F gi = gipow.at(c1);
 #pragma unroll
     for (int c2 = 0; c2 < N; c2++)
-        store_fr(h + (size_t)N * q + brev_bits((uint32_t)c2, logN),
-                 x[c2] * R.cs[c2] * gi - load_fr(ccoef + (size_t)c2 * chunk + q));
+        st_fr(h + (size_t)N * q + brev_bits((uint32_t)c2, logN),
+                 x[c2] * R.cs[c2] * gi - ld_fr(ccoef + (size_t)c2 * chunk + q));
 }
 
 template <class F>

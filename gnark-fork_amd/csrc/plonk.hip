@@ -25,22 +25,6 @@ void xn_minus_one_inv(gg_domain* big, size_t n_small, void* out);
 namespace gg {
 namespace plk {
 
-template <class F>
-__device__ __forceinline__ F ldf(const F* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    uint4 a = q[0], b = q[1];
-    F r;
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-    return r;
-}
-template <class F>
-__device__ __forceinline__ void stf(F* p, const F& r) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
-
 // sum c[k] x^k: nc - 1 products (the leading coefficient starts the chain)
 template <class F>
 __device__ __forceinline__ F horner_d(const F* c, int nc, const F& x) {
@@ -54,14 +38,14 @@ __device__ __forceinline__ F horner_d(const F* c, int nc, const F& x) {
 template <class F>
 __device__ __forceinline__ F numerator_at(const NumParamsT<F>& P, uint32_t j) {
     const F one = F::one();
-    F L = ldf(P.x[ID_L] + j), R = ldf(P.x[ID_R] + j), O = ldf(P.x[ID_O] + j);
-    F Z = ldf(P.x[ID_Z] + j);
+    F L = ld_fr(P.x[ID_L] + j), R = ld_fr(P.x[ID_R] + j), O = ld_fr(P.x[ID_O] + j);
+    F Z = ld_fr(P.x[ID_Z] + j);
     const uint32_t j1 = j + 1 == P.n ? 0 : j + 1;
-    F ZS = P.x[ID_ZS] ? ldf(P.x[ID_ZS] + (P.zs_shift ? j1 : j)) : ldf(P.x[ID_Z] + j1);
-    F S1 = ldf(P.x[ID_S1] + j) * P.beta, S2 = ldf(P.x[ID_S2] + j) * P.beta,
-        S3 = ldf(P.x[ID_S3] + j) * P.beta;
+    F ZS = P.x[ID_ZS] ? ld_fr(P.x[ID_ZS] + (P.zs_shift ? j1 : j)) : ld_fr(P.x[ID_Z] + j1);
+    F S1 = ld_fr(P.x[ID_S1] + j) * P.beta, S2 = ld_fr(P.x[ID_S2] + j) * P.beta,
+        S3 = ld_fr(P.x[ID_S3] + j) * P.beta;
     // blinding: bl/br/bo/bz evaluated at twiddles0[j], bz at twiddles0[(j+1) % n] for ZS
-    const F t0 = ldf(P.tw0 + j), t1 = P.tw1 ? ldf(P.tw1 + j) : ldf(P.tw0 + j1);
+    const F t0 = ld_fr(P.tw0 + j), t1 = P.tw1 ? ld_fr(P.tw1 + j) : ld_fr(P.tw0 + j1);
     L = L + horner_d(P.bcoef[0], P.bdeg[0], t0);
     R = R + horner_d(P.bcoef[1], P.bdeg[1], t0);
     O = O + horner_d(P.bcoef[2], P.bdeg[2], t0);
@@ -69,11 +53,11 @@ __device__ __forceinline__ F numerator_at(const NumParamsT<F>& P, uint32_t j) {
     ZS = ZS + horner_d(P.bcoef[3], P.bdeg[3], t1);
     // gateConstraint
     // ql L + qm L R = L (ql + qm R): four products instead of five
-    F ic = L * (ldf(P.x[ID_QL] + j) + ldf(P.x[ID_QM] + j) * R) + ldf(P.x[ID_QR] + j) * R;
-    ic = ic + ldf(P.x[ID_QO] + j) * O + ldf(P.x[ID_QK] + j);
-    for (int q = ID_QCI; q + 1 < P.nx; q += 2) ic = ic + ldf(P.x[q] + j) * ldf(P.x[q + 1] + j);
+    F ic = L * (ld_fr(P.x[ID_QL] + j) + ld_fr(P.x[ID_QM] + j) * R) + ld_fr(P.x[ID_QR] + j) * R;
+    ic = ic + ld_fr(P.x[ID_QO] + j) * O + ld_fr(P.x[ID_QK] + j);
+    for (int q = ID_QCI; q + 1 < P.nx; q += 2) ic = ic + ld_fr(P.x[q] + j) * ld_fr(P.x[q + 1] + j);
     // orderingConstraint
-    const F id = ldf(P.x[ID_ID] + j);
+    const F id = ld_fr(P.x[ID_ID] + j);
     F a = P.gamma + L + id * P.ka, b = id * P.kb + R + P.gamma, c = id * P.kc + O + P.gamma;
     F r = a * b * c * Z;
     a = S1 + L + P.gamma;
@@ -81,7 +65,7 @@ __device__ __forceinline__ F numerator_at(const NumParamsT<F>& P, uint32_t j) {
     c = S3 + O + P.gamma;
     F l = a * b * c * ZS - r;
     // ratioLocalConstraint
-    F rl = (Z - one) * ldf(P.x[ID_LONE] + j);
+    F rl = (Z - one) * ld_fr(P.x[ID_LONE] + j);
     const F res = (rl * P.alpha + l) * P.alpha + ic;
     return P.has_out_scale ? res * P.out_scale : res;
 }
@@ -94,7 +78,7 @@ __global__ void __launch_bounds__(256) k_numerator_coset(NumParamsT<F> P) {
     const F res = numerator_at(P, j);
     uint32_t pos = P.log_big ? __brev(P.rho * j + P.coset) >> (32 - P.log_big) : 0u;
     if (P.local_block) pos &= P.n - 1;
-    stf(P.cres + pos, res);
+    st_fr(P.cres + pos, res);
 }
 
 // n >= 256: 16 x 16 tiles.  Thread t of block m computes j = h 2^(L-4) + 16 m + l
@@ -123,7 +107,7 @@ __global__ void __launch_bounds__(256) k_numerator_coset_tiled(NumParamsT<F> P, 
     F o;
 #pragma unroll
     for (int k = 0; k < 8; k++) o.v[k] = tile[k][t + (t >> 5)];
-    stf(P.cres + pos, o);
+    st_fr(P.cres + pos, o);
 }
 
 template <class F>
@@ -135,7 +119,7 @@ __global__ void k_mul_periodic_bitrev(F* r, size_t n, int log_n, PeriodicTab<F> 
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint32_t irev = log_n ? (__brev((uint32_t)i) >> (32 - log_n)) : 0u;
-    stf(r + i, ldf(r + i) * t.f[irev % rho]);
+    st_fr(r + i, ld_fr(r + i) * t.f[irev % rho]);
 }
 
 // Montgomery batch inversion: thread t owns elements t, t+T, ... (zeros skipped)
@@ -145,18 +129,18 @@ __global__ void __launch_bounds__(256) k_batch_invert(F* a, size_t n, size_t T, 
     if (t >= T || t >= n) return;
     F acc = F::one();
     for (size_t i = t; i < n; i += T) {
-        stf(prefix + i, acc);
-        F x = ldf(a + i);
+        st_fr(prefix + i, acc);
+        F x = ld_fr(a + i);
         if (!x.is_zero()) acc = acc * x;
     }
     F inv = inverse(acc);
     size_t last = t + ((n - 1 - t) / T) * T;
     for (size_t i = last;; i -= T) {
-        F x = ldf(a + i);
+        F x = ld_fr(a + i);
         if (!x.is_zero()) {
-            F xi = inv * ldf(prefix + i);
+            F xi = inv * ld_fr(prefix + i);
             inv = inv * x;
-            stf(a + i, xi);
+            st_fr(a + i, xi);
         }
         if (i < T) break;
     }
@@ -182,9 +166,9 @@ __global__ void __launch_bounds__(256) k_fold_brev(const F* in, size_t m, int S,
     F acc = F::zero();
     for (int t = S - 1; t >= 0; t--) {
         const uint32_t bt = logS ? (__brev((uint32_t)t) >> (32 - logS)) : 0u;
-        acc = acc * kappa + ldf(in + (size_t)S * k + bt);
+        acc = acc * kappa + ld_fr(in + (size_t)S * k + bt);
     }
-    stf(out + k, acc);
+    st_fr(out + k, acc);
 }
 
 template <class F>
@@ -201,7 +185,7 @@ template <class F>
 __global__ void k_gather_strided(const F* in, size_t n, int S, int s, F* out) {
     const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n / S) return;
-    stf(out + j, ldf(in + ((size_t)s + (size_t)S * j) % n));
+    st_fr(out + j, ld_fr(in + ((size_t)s + (size_t)S * j) % n));
 }
 
 template <class F>

@@ -24,24 +24,6 @@
 namespace gg {
 namespace plk {
 
-namespace {
-template <class F>
-__device__ __forceinline__ F ldb(const F* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    uint4 a = q[0], b = q[1];
-    F r;
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-    return r;
-}
-template <class F>
-__device__ __forceinline__ void stb(F* p, const F& r) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
-}  // namespace
-
 constexpr int SCAN_PER = 8;                    // elements per thread
 constexpr int SCAN_BLK = 256 * SCAN_PER;       // elements per block
 enum { SCAN_PROD = 0, SCAN_AFFINE = 1 };
@@ -63,7 +45,7 @@ __global__ void __launch_bounds__(256) k_scan_local(F* x, size_t m, ScanPow<F> P
     F v[SCAN_PER];
     const F id = MODE == SCAN_PROD ? F::one() : F::zero();
 #pragma unroll
-    for (int k = 0; k < SCAN_PER; k++) v[k] = base + k < m ? ldb(x + base + k) : id;
+    for (int k = 0; k < SCAN_PER; k++) v[k] = base + k < m ? ld_fr(x + base + k) : id;
 #pragma unroll
     for (int k = 1; k < SCAN_PER; k++) v[k] = MODE == SCAN_PROD ? v[k] * v[k - 1] : v[k] + P.p[1] * v[k - 1];
     F agg = v[SCAN_PER - 1];
@@ -99,32 +81,32 @@ __global__ void __launch_bounds__(256) k_scan_local(F* x, size_t m, ScanPow<F> P
     }
 #pragma unroll
     for (int k = 0; k < SCAN_PER; k++)
-        if (base + k < m) stb(x + base + k, v[k]);
-    if (threadIdx.x == 255 && aux) stb(aux + blockIdx.x, agg);
+        if (base + k < m) st_fr(x + base + k, v[k]);
+    if (threadIdx.x == 255 && aux) st_fr(aux + blockIdx.x, agg);
 }
 
 // x[e] (block b > 0) combined with the inclusive aggregate of blocks < b
 template <class F, int MODE>
 __global__ void __launch_bounds__(256) k_scan_fix(F* x, size_t m, ScanPow<F> P, const F* aux) {
     const size_t b = blockIdx.x + 1;
-    const F c = ldb(aux + b - 1);
+    const F c = ld_fr(aux + b - 1);
     const uint32_t o0 = threadIdx.x * SCAN_PER;
     const size_t base = b * SCAN_BLK + o0;
     F f;
     if (MODE == SCAN_AFFINE) {
         const uint32_t e = o0 + 1;  // u^(offset + 1)
-        f = ldb(P.hi + (e >> 6)) * ldb(P.lo + (e & 63)) * c;
+        f = ld_fr(P.hi + (e >> 6)) * ld_fr(P.lo + (e & 63)) * c;
     }
 #pragma unroll
     for (int k = 0; k < SCAN_PER; k++) {
         if (base + k >= m) break;
-        F v = ldb(x + base + k);
+        F v = ld_fr(x + base + k);
         if (MODE == SCAN_PROD) v = v * c;
         else {
             v = v + f;
             f = f * P.p[1];
         }
-        stb(x + base + k, v);
+        st_fr(x + base + k, v);
     }
 }
 
@@ -161,13 +143,13 @@ __global__ void k_pow_tab(F u, F* tab) {
     const uint32_t t = threadIdx.x;
     if (blockIdx.x || t >= 97) return;
     if (t < 64) {
-        stb(tab + t, pow_small(u, t));
+        st_fr(tab + t, pow_small(u, t));
         return;
     }
     F u64 = u;
 #pragma unroll
     for (int k = 0; k < 6; k++) u64 = u64 * u64;
-    stb(tab + t, pow_small(u64, t - 64));  // j = t - 64 <= 32
+    st_fr(tab + t, pow_small(u64, t - 64));  // j = t - 64 <= 32
 }
 
 size_t scan_arena_bytes(size_t m) {
@@ -214,14 +196,14 @@ void scan_prod(F* x, size_t m, hipStream_t st, Arena& ar) {
 template <class F>
 __global__ void k_reverse_copy(F* dst, const F* src, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) stb(dst + i, ldb(src + n - 1 - i));
+    if (i < n) st_fr(dst + i, ld_fr(src + n - 1 - i));
 }
 
 // q[j] = g[n-2-j] for j < n-1 where g is the reversed affine scan
 template <class F>
 __global__ void k_quotient_out(F* q, const F* g, size_t n) {
     size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j + 1 < n) stb(q + j, ldb(g + n - 2 - j));
+    if (j + 1 < n) st_fr(q + j, ld_fr(g + n - 2 - j));
 }
 
 // ---------------------------------------------------------------- ratio
@@ -230,7 +212,7 @@ struct PowSplit {  // x^e = hi[e >> S] * lo[e & (2^S - 1)]
     const F *hi, *lo;
     int S;
     __device__ __forceinline__ F at(uint32_t e) const {
-        return ldb(hi + (e >> S)) * ldb(lo + (e & ((1u << S) - 1)));
+        return ld_fr(hi + (e >> S)) * ld_fr(lo + (e & ((1u << S) - 1)));
     }
 };
 
@@ -242,8 +224,8 @@ __global__ void __launch_bounds__(256) k_ratio_numden(const F* L, const F* R, co
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (i == 0) {
-        stb(num, F::one());
-        stb(den, F::one());
+        st_fr(num, F::one());
+        st_fr(den, F::one());
     }
     if (i + 1 >= n) return;
     const F* f[3] = {L, R, O};
@@ -251,7 +233,7 @@ __global__ void __launch_bounds__(256) k_ratio_numden(const F* L, const F* R, co
     F b = F::one(), d = F::one();
 #pragma unroll
     for (int j = 0; j < 3; j++) {
-        const F fv = ldb(f[j] + i);
+        const F fv = ld_fr(f[j] + i);
         F id = j == 0 ? wi : (j == 1 ? wi * u : wi * uu);
         b = b * (fv + beta * id + gamma);
         const uint64_t s = (uint64_t)perm[(size_t)j * n + i];
@@ -261,14 +243,14 @@ __global__ void __launch_bounds__(256) k_ratio_numden(const F* L, const F* R, co
         else if (blk == 2) sg = sg * uu;
         d = d * (fv + beta * sg + gamma);
     }
-    stb(num + i + 1, b);
-    stb(den + i + 1, d);
+    st_fr(num + i + 1, b);
+    st_fr(den + i + 1, d);
 }
 
 template <class F>
 __global__ void k_mul_inplace(F* a, const F* b, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) stb(a + i, ldb(a + i) * ldb(b + i));
+    if (i < n) st_fr(a + i, ld_fr(a + i) * ld_fr(b + i));
 }
 
 // ---------------------------------------------------------------- foldH / linearized
@@ -276,8 +258,8 @@ template <class F>
 __global__ void k_fold_h(const F* h, size_t np2, F z, F* out) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= np2) return;
-    F t = ldb(h + 2 * np2 + i) * z + ldb(h + np2 + i);
-    stb(out + i, t * z + ldb(h + i));
+    F t = ld_fr(h + 2 * np2 + i) * z + ld_fr(h + np2 + i);
+    st_fr(out + i, t * z + ld_fr(h + i));
 }
 
 // prove.go:1347-1386, term by term
@@ -285,18 +267,18 @@ template <class F>
 __global__ void __launch_bounds__(256) k_linearized(LinParamsT<F> P) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P.nz) return;
-    const F zi = ldb(P.z + i);
+    const F zi = ld_fr(P.z + i);
     F t = zi * P.s2;
-    if (i < P.ns3) t = t + ldb(P.s3 + i) * P.s1;
+    if (i < P.ns3) t = t + ld_fr(P.s3 + i) * P.s1;
     t = t * P.alpha;
     if (i < P.nq) {
-        F t0 = ldb(P.ql + i) * P.l + ldb(P.qm + i) * P.rl;
+        F t0 = ld_fr(P.ql + i) * P.l + ld_fr(P.qm + i) * P.rl;
         t = t + t0;
-        t = t + ldb(P.qr + i) * P.r;
-        t = t + (ldb(P.qo + i) * P.o + ldb(P.qk + i));
-        for (int j = 0; j < P.ncmt; j++) t = t + ldb(P.pi2[j] + i) * P.qcp[j];
+        t = t + ld_fr(P.qr + i) * P.r;
+        t = t + (ld_fr(P.qo + i) * P.o + ld_fr(P.qk + i));
+        for (int j = 0; j < P.ncmt; j++) t = t + ld_fr(P.pi2[j] + i) * P.qcp[j];
     }
-    stb(P.z + i, t + zi * P.lag);
+    st_fr(P.z + i, t + zi * P.lag);
 }
 
 // out[bitrev(i)] = in[i] (out-of-place; fft.BitReverse / iop ToRegular)
@@ -305,25 +287,25 @@ __global__ void k_bit_reverse(F* out, const F* in, size_t n, int log_n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint32_t r = log_n ? (__brev((uint32_t)i) >> (32 - log_n)) : 0u;
-    stb(out + r, ldb(in + i));
+    st_fr(out + r, ld_fr(in + i));
 }
 
 // y[i] += a * x[i]
 template <class F>
 __global__ void k_axpy(F* y, const F* x, size_t n, F a) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) stb(y + i, ldb(y + i) + a * ldb(x + i));
+    if (i < n) st_fr(y + i, ld_fr(y + i) + a * ld_fr(x + i));
 }
 
 template <class F>
 __global__ void k_scale(F* y, size_t n, F a) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) stb(y + i, ldb(y + i) * a);
+    if (i < n) st_fr(y + i, ld_fr(y + i) * a);
 }
 template <class F>
 __global__ void k_shift_copy(const F* in, F* out, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) stb(out + i, ldb(in + (i + 1 == n ? 0 : i + 1)));
+    if (i < n) st_fr(out + i, ld_fr(in + (i + 1 == n ? 0 : i + 1)));
 }
 
 size_t horner_arena_bytes(size_t n) { return ((n * 32 + 255) & ~(size_t)255) + scan_arena_bytes(n); }
@@ -361,8 +343,8 @@ __global__ void k_pow_split(F w, F step, F* lo, uint32_t nlo, F* hi, uint32_t nh
         }
         return r;
     };
-    if (t < nlo) stb(lo + t, pw(w, t));
-    if (t < nhi) stb(hi + t, pw(step, t));
+    if (t < nlo) st_fr(lo + t, pw(w, t));
+    if (t < nhi) st_fr(hi + t, pw(step, t));
 }
 
 static int log2_ceil(size_t n) {
@@ -424,8 +406,8 @@ __global__ void __launch_bounds__(256) k_eval_many(EvalJob<F> J, PowSplit<F> ap,
         if (g < len) {
             const uint32_t jn = (len - 1 - g) / G;  // last j with g + j G < len
             const F* f = J.f[k];
-            acc = ldb(f + g + (size_t)jn * G);
-            for (uint32_t j = jn; j-- > 0;) acc = acc * aG + ldb(f + g + (size_t)j * G);
+            acc = ld_fr(f + g + (size_t)jn * G);
+            for (uint32_t j = jn; j-- > 0;) acc = acc * aG + ld_fr(f + g + (size_t)j * G);
             acc = acc * ag;
         }
         // block sum (LDS, limb-major)
@@ -443,7 +425,7 @@ __global__ void __launch_bounds__(256) k_eval_many(EvalJob<F> J, PowSplit<F> ap,
             }
             __syncthreads();
         }
-        if (threadIdx.x == 0) stb(part + (size_t)k * gridDim.x + blockIdx.x, acc);
+        if (threadIdx.x == 0) st_fr(part + (size_t)k * gridDim.x + blockIdx.x, acc);
         __syncthreads();
     }
 }
@@ -454,7 +436,7 @@ __global__ void __launch_bounds__(256) k_eval_sum(const F* part, uint32_t nb, F*
     __shared__ uint32_t sh[256 * 8];
     const int k = blockIdx.x;
     F acc = F::zero();
-    for (uint32_t b = threadIdx.x; b < nb; b += blockDim.x) acc = acc + ldb(part + (size_t)k * nb + b);
+    for (uint32_t b = threadIdx.x; b < nb; b += blockDim.x) acc = acc + ld_fr(part + (size_t)k * nb + b);
 #pragma unroll
     for (int l = 0; l < 8; l++) sh[l * 256 + threadIdx.x] = acc.v[l];
     __syncthreads();
@@ -469,7 +451,7 @@ __global__ void __launch_bounds__(256) k_eval_sum(const F* part, uint32_t nb, F*
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) stb(out + k, acc);
+    if (threadIdx.x == 0) st_fr(out + k, acc);
 }
 
 size_t eval_many_arena_bytes(size_t max_len, int count) {
@@ -526,8 +508,8 @@ __global__ void __launch_bounds__(256) k_lincomb(F* out, size_t n_out, LinComb<F
     if (j >= n_out) return;
     F acc = F::zero();
     for (int k = 0; k < L.count; k++)
-        if (j < L.len[k]) acc = acc + L.c[k] * ldb(L.f[k] + j);
-    stb(out + j, acc);
+        if (j < L.len[k]) acc = acc + L.c[k] * ld_fr(L.f[k] + j);
+    st_fr(out + j, acc);
 }
 
 template <class F>
@@ -559,7 +541,7 @@ __global__ void __launch_bounds__(256) k_ratio_factors(const F* L, const F* R, c
     F b = F::one(), d = F::one();
 #pragma unroll
     for (int j = 0; j < 3; j++) {
-        const F fv = ldb(f[j] + t);
+        const F fv = ld_fr(f[j] + t);
         F id = j == 0 ? wi : (j == 1 ? wi * u : wi * uu);
         b = b * (fv + beta * id + gamma);
         const uint64_t s = (uint64_t)pm[j][t];
@@ -569,15 +551,15 @@ __global__ void __launch_bounds__(256) k_ratio_factors(const F* L, const F* R, c
         else if (blk == 2) sg = sg * uu;
         d = d * (fv + beta * sg + gamma);
     }
-    stb(num + t, b);
-    stb(den + t, d);
+    st_fr(num + t, b);
+    st_fr(den + t, d);
 }
 
 template <class F>
 __global__ void k_ratio_fixup(const F* P, size_t cnt, F prefix, F* z) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= cnt) return;
-    stb(z + t, t ? prefix * ldb(P + t - 1) : prefix);
+    st_fr(z + t, t ? prefix * ld_fr(P + t - 1) : prefix);
 }
 
 size_t ratio_range_arena_bytes(size_t n, size_t cnt) {

@@ -34,22 +34,6 @@ namespace pls {
 
 enum { T_UPLOAD, T_TRACE, T_PERM, T_SGATHER, T_INTT, T_EC_STAGES, T_EC_NORM, T_TOTAL, T_PK_BOUNCE, T_PK_BUILD, T_SLOTS };
 
-template <class F>
-__device__ __forceinline__ F ldfr(const F* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    uint4 a = q[0], b = q[1];
-    F r;
-    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-    return r;
-}
-template <class F>
-__device__ __forceinline__ void stfr(F* p, const F& r) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
-
 // rows i < nb_public: ql = -1; row nb_public + c: the coefficients of constraint
 // c (qidx: qL, qR, qO, qM, qC); the padding rows: 0
 template <class F>
@@ -62,23 +46,23 @@ __global__ void __launch_bounds__(256) k_trace(const uint32_t* qidx, const F* co
         l = -F::one();
     } else if (i - nb_public < ncons) {
         const uint32_t* q = qidx + 5 * (size_t)(i - nb_public);
-        l = ldfr(coef + q[0]);
-        r = ldfr(coef + q[1]);
-        o = ldfr(coef + q[2]);
-        m = ldfr(coef + q[3]);
-        k = ldfr(coef + q[4]);
+        l = ld_fr(coef + q[0]);
+        r = ld_fr(coef + q[1]);
+        o = ld_fr(coef + q[2]);
+        m = ld_fr(coef + q[3]);
+        k = ld_fr(coef + q[4]);
     }
-    stfr(ql + i, l);
-    stfr(qr + i, r);
-    stfr(qm + i, m);
-    stfr(qo + i, o);
-    stfr(qk + i, k);
+    st_fr(ql + i, l);
+    st_fr(qr + i, r);
+    st_fr(qm + i, m);
+    st_fr(qo + i, o);
+    st_fr(qk + i, k);
 }
 // qcp[nb_public + committed[t]] = 1, t < cnt (committed[t] < ncons checked on the host)
 template <class F>
 __global__ void __launch_bounds__(256) k_qcp(const uint32_t* committed, uint32_t cnt, uint32_t nb_public, F* qcp) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < cnt) stfr(qcp + nb_public + committed[t], F::one());
+    if (t < cnt) st_fr(qcp + nb_public + committed[t], F::one());
 }
 // lro (setup.go:316-330) as sort keys, the slot numbers as values
 __global__ void __launch_bounds__(256) k_lro(const uint32_t* wires, uint32_t n, uint32_t nb_public, uint32_t ncons,
@@ -115,7 +99,7 @@ __global__ void __launch_bounds__(256) k_link(const uint32_t* key, const uint32_
 template <class F>
 __global__ void __launch_bounds__(256) k_fill_geo(F* x, size_t n, F first, F ratio) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) stfr(x + i, i ? ratio : first);
+    if (i < n) st_fr(x + i, i ? ratio : first);
 }
 // S[s] = ID[perm[s]], ID[q] = shift[q div n] * omega^(q mod n); s < 3n
 template <class F>
@@ -129,10 +113,10 @@ __global__ void __launch_bounds__(256) k_sgather(const int64_t* perm, const F* w
     if (s >= 3u * n) return;
     const uint32_t q = (uint32_t)perm[s];
     const uint32_t blk = q >> log_n;
-    F v = ldfr(wpow + (q & (n - 1u)));
+    F v = ld_fr(wpow + (q & (n - 1u)));
     if (blk) v = v * sh.u[blk];
     const uint32_t col = s >> log_n, i = s & (n - 1u);
-    stfr((col == 0 ? s1 : col == 1 ? s2 : s3) + i, v);
+    st_fr((col == 0 ? s1 : col == 1 ? s2 : s3) + i, v);
 }
 
 struct Timer {
@@ -269,17 +253,13 @@ void run_setup(const Args& a, SetupH* h) {
     const size_t nb = 32 * n;
     const uint32_t n32 = (uint32_t)n, npub = (uint32_t)a.nb_public, ncons = (uint32_t)a.ncons;
 
-    auto up = [&](DevBuf& b, const void* src, size_t bytes) {
-        b.alloc(std::max<size_t>(bytes, 16));
-        if (bytes) GG_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
-    };
     DevBuf d_wires, d_qidx, d_coef, d_committed;
-    up(d_wires, a.wires, a.ncons * 12);
-    up(d_qidx, a.qidx, a.ncons * 20);
-    up(d_coef, a.coeffs, a.ncoef * 32);
-    up(d_committed, a.committed, a.n_cmt ? (size_t)a.coff[a.n_cmt] * 4 : 0);
-    up(h->kzg, a.kzg, (n + 3) * h->pt);
-    if (a.lag) up(h->lag, a.lag, n * h->pt);
+    upload(d_wires, a.wires, a.ncons * 12, st);
+    upload(d_qidx, a.qidx, a.ncons * 20, st);
+    upload(d_coef, a.coeffs, a.ncoef * 32, st);
+    upload(d_committed, a.committed, a.n_cmt ? (size_t)a.coff[a.n_cmt] * 4 : 0, st);
+    upload(h->kzg, a.kzg, (n + 3) * h->pt, st);
+    if (a.lag) upload(h->lag, a.lag, n * h->pt, st);
     else h->lag.alloc(n * h->pt);
     GG_WAIT_STREAM(st);
     h->ms[T_UPLOAD] = tm.lap();

@@ -98,13 +98,13 @@ def hint_eval_host(curve: str, hid: int, inputs: Sequence[int], n_out: int) -> l
 
 def _hint_order(hints, n_constraints):
     """Instruction order: ("h", i) / ("c", j), hint i just before constraint hints[i].before."""
-    at = [[] for _ in range(n_constraints + 1)]
+    at = {}
     for i, h in enumerate(hints):
         if not 0 <= h.before <= n_constraints:
             raise ValueError("hint %d: before=%d outside [0, %d]" % (i, h.before, n_constraints))
-        at[h.before].append(i)
+        at.setdefault(h.before, []).append(i)
     for c in range(n_constraints + 1):
-        for i in at[c]:
+        for i in at.get(c, ()):
             yield "h", i
         if c < n_constraints:
             yield "c", c
@@ -187,85 +187,117 @@ def _hint_arrays(hints, hint_levels, coeff_index):
     return [u32(a) for a in (ids, in_off, expr_off, tw, tc, o0, o1, lo, lh)], len(hint_levels)
 
 
-def _set_hints(fn, handle, hints, hint_levels, coeff_index):
-    arrs, n_levels = _hint_arrays(hints, hint_levels, coeff_index)
-    check(fn(handle, len(hints), *(ptr(a) for a in arrs), n_levels))
-
-
-def _schedule(fn, handle):
-    s, nl, ns = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_size_t()
-    check(fn(handle, ctypes.byref(s), ctypes.byref(nl), ctypes.byref(ns)))
-    return bool(s.value), nl.value, ns.value
-
-
 def compute_levels(nb_inputs: int, n_wires: int, term_off, term_wire) -> list:
     """r1cs.Levels from the CSR terms (blueprint_r1cs.go:61-96, core.go:405-419):
     wires < nb_inputs are inputs (not in the instruction tree)."""
-    level = np.full(n_wires, -1, dtype=np.int64)
-    ncons = (len(term_off) - 1) // 3
-    out = []
-    for c in range(ncons):
-        lo, hi = int(term_off[3 * c]), int(term_off[3 * c + 3])
-        mx, outs = -1, []
-        for w in term_wire[lo:hi]:
-            w = int(w)
-            if w < nb_inputs:
-                continue
-            if level[w] < 0:
-                outs.append(w)
-            elif level[w] > mx:
-                mx = int(level[w])
-        mx += 1
-        for w in outs:
-            level[w] = mx
-        while len(out) <= mx:
-            out.append([])
-        out[mx].append(c)
-    return out
+    return compute_levels_with_hints(nb_inputs, n_wires, term_off, term_wire, ())[0]
 
 
-class R1CS:
-    """Device-resident R1CS (gg_r1cs_create) with its solver."""
+def compute_scs_levels(nb_inputs: int, n_wires: int, wires) -> list:
+    """r1cs.Levels of a sparse R1CS (blueprint.go updateInstructionTree over
+    xa, xb, xc): wires < nb_inputs are the witness."""
+    return compute_scs_levels_with_hints(nb_inputs, n_wires, wires, ())[0]
 
-    def __init__(self, nb_public: int, nb_secret: int, n_wires: int, term_off, term_wire, term_coeff,
-                 coeffs: Sequence[int], levels: Optional[Sequence[Sequence[int]]] = None,
-                 curve: str = "bn254", hints=None, hint_levels=None):
+
+def _intern(table, index, k):
+    """Index of coefficient k in table, appended when new (r1cs.Coefficients)."""
+    if k not in index:
+        index[k] = len(table)
+        table.append(k)
+    return index[k]
+
+
+class _System:
+    """What R1CS and SparseR1CS share: the scalar field, the levels and the
+    coefficient table as the library takes them, the hints, and the handle's
+    schedule / release / error mapping.  A subclass names its C functions."""
+    _set_hints_fn = _schedule_fn = _release_fn = None
+
+    def _field(self, curve, bn254):
+        """Sets curve, mod and the Montgomery conversion; returns the GG_CURVE_* id."""
         from ._lib import GG_CURVE_BN254, GG_CURVE_BLS12_381
         self.curve = curve
-        self.mod = fr.R if curve == "bn254" else fr.BLS_R
-        self._mont = fr.fr_mont if curve == "bn254" else fr.bls_fr_mont
-        self.nb_public, self.nb_secret, self.n_wires = nb_public, nb_secret, n_wires
-        self.term_off = np.ascontiguousarray(term_off, dtype=np.uint32)
-        self.term_wire = np.ascontiguousarray(term_wire, dtype=np.uint32)
-        self.term_coeff = np.ascontiguousarray(term_coeff, dtype=np.uint32)
-        self.n_constraints = (len(self.term_off) - 1) // 3
+        self.mod = fr.R if bn254 else fr.BLS_R
+        self._mont = fr.fr_mont if bn254 else fr.bls_fr_mont
+        return GG_CURVE_BN254 if bn254 else GG_CURVE_BLS12_381
+
+    def _set_levels(self, hints, levels, hint_levels, compute):
+        """self.hints / levels / hint_levels; compute(hints) -> (levels, hint_levels)
+        fills in what the caller left out.  Returns the levels flattened:
+        (level_off, level_cons) of gg_*_create."""
         self.hints = list(hints) if hints else None
         if self.hints and (levels is None or hint_levels is None):
-            levels, hint_levels = compute_levels_with_hints(nb_public + nb_secret, n_wires, self.term_off,
-                                                            self.term_wire, self.hints)
+            levels, hint_levels = compute(self.hints)
         if levels is None:
-            levels = compute_levels(nb_public + nb_secret, n_wires, self.term_off, self.term_wire)
+            levels = compute(())[0]
         self.levels, self.hint_levels = levels, hint_levels
         lo = np.zeros(len(levels) + 1, dtype=np.uint32)
         lo[1:] = np.cumsum([len(x) for x in levels])
         lc = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint32) for x in levels])
                                   if levels else np.zeros(0, dtype=np.uint32), dtype=np.uint32)
-        cbytes = b"".join(self._mont(int(k) % self.mod) for k in coeffs)
+        return lo, lc
+
+    def _coeff_bytes(self, coeffs):
+        return b"".join(self._mont(int(k) % self.mod) for k in coeffs)
+
+    def _set_own_hints(self, coeffs):
+        if self.hints:
+            index = {int(k) % self.mod: i for i, k in reversed(list(enumerate(coeffs)))}
+            self.set_hints(self.hints, self.hint_levels, lambda k: index[int(k) % self.mod])
+
+    def set_hints(self, hints, hint_levels, coeff_index):
+        """gg_*_set_hints: once, before the first solve."""
+        arrs, n_levels = _hint_arrays(hints, hint_levels, coeff_index)
+        check(self._set_hints_fn(self.handle, len(hints), *(ptr(a) for a in arrs), n_levels))
+
+    def schedule(self):
+        """(strands, launches, segments) of the last solve (gg_*_schedule)."""
+        s, nl, ns = ctypes.c_int(), ctypes.c_size_t(), ctypes.c_size_t()
+        check(self._schedule_fn(self.handle, ctypes.byref(s), ctypes.byref(nl), ctypes.byref(ns)))
+        return bool(s.value), nl.value, ns.value
+
+    @staticmethod
+    def _raise_for(rc, bad):
+        if rc == GG_ERR_UNSATISFIED:
+            raise UnsatisfiedConstraintError(bad.value, lib.gg_last_error().decode())
+        check(rc)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._release_fn(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class R1CS(_System):
+    """Device-resident R1CS (gg_r1cs_create) with its solver."""
+    _set_hints_fn, _schedule_fn, _release_fn = lib.gg_r1cs_set_hints, lib.gg_r1cs_schedule, lib.gg_r1cs_release
+
+    def __init__(self, nb_public: int, nb_secret: int, n_wires: int, term_off, term_wire, term_coeff,
+                 coeffs: Sequence[int], levels: Optional[Sequence[Sequence[int]]] = None,
+                 curve: str = "bn254", hints=None, hint_levels=None):
+        cid = self._field(curve, curve == "bn254")
+        self.nb_public, self.nb_secret, self.n_wires = nb_public, nb_secret, n_wires
+        self.term_off = np.ascontiguousarray(term_off, dtype=np.uint32)
+        self.term_wire = np.ascontiguousarray(term_wire, dtype=np.uint32)
+        self.term_coeff = np.ascontiguousarray(term_coeff, dtype=np.uint32)
+        self.n_constraints = (len(self.term_off) - 1) // 3
+        lo, lc = self._set_levels(hints, levels, hint_levels, lambda hs: compute_levels_with_hints(
+            nb_public + nb_secret, n_wires, self.term_off, self.term_wire, hs))
+        cbytes = self._coeff_bytes(coeffs)
         h = ctypes.c_void_p()
-        check(lib.gg_r1cs_create_ex(GG_CURVE_BN254 if curve == "bn254" else GG_CURVE_BLS12_381, n_wires,
-                                    self.n_constraints, ptr(self.term_off), ptr(self.term_wire),
+        check(lib.gg_r1cs_create_ex(cid, n_wires, self.n_constraints, ptr(self.term_off), ptr(self.term_wire),
                                     ptr(self.term_coeff), ptr(cbytes), len(coeffs), ptr(lo), ptr(lc),
-                                    len(levels), ctypes.byref(h)))
+                                    len(self.levels), ctypes.byref(h)))
         self.handle = h
         # newSolver's witness-size check, enforced by the library too (solver.go:71-76)
         check(lib.gg_r1cs_set_inputs(h, nb_public, nb_secret))
-        if self.hints:
-            index = {int(k) % self.mod: i for i, k in reversed(list(enumerate(coeffs)))}
-            self.set_hints(self.hints, hint_levels, lambda k: index[int(k) % self.mod])
-
-    def set_hints(self, hints, hint_levels, coeff_index):
-        """gg_r1cs_set_hints: once, before the first solve."""
-        _set_hints(lib.gg_r1cs_set_hints, self.handle, hints, hint_levels, coeff_index)
+        self._set_own_hints(coeffs)
 
     @classmethod
     def from_terms(cls, nb_public: int, nb_secret: int, n_wires: int, constraints, levels=None,
@@ -279,20 +311,13 @@ class R1CS:
         for L, R, O in constraints:
             for side in (L, R, O):
                 for w, k in side:
-                    k %= mod
-                    if k not in index:
-                        index[k] = len(table)
-                        table.append(k)
                     wires.append(w)
-                    cids.append(index[k])
+                    cids.append(_intern(table, index, k % mod))
                 off.append(len(wires))
         for h in hints or ():
             for expr in h.inputs:
                 for _, k in expr:
-                    k %= mod
-                    if k not in index:
-                        index[k] = len(table)
-                        table.append(k)
+                    _intern(table, index, k % mod)
         if not table:
             table = [1]
         return cls(nb_public, nb_secret, n_wires, off, wires, cids, table, levels, curve, hints, hint_levels)
@@ -301,10 +326,6 @@ class R1CS:
         a, b, c = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
         check(lib.gg_r1cs_info(self.handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value
-
-    def schedule(self):
-        """(strands, launches, segments) of the last solve (gg_r1cs_schedule)."""
-        return _schedule(lib.gg_r1cs_schedule, self.handle)
 
     def solve(self, witness, on_device: bool = True):
         """r1cs.Solve(fullWitness): witness = public (without ONE_WIRE) then
@@ -331,9 +352,7 @@ class R1CS:
         bad = ctypes.c_int64(-1)
         rc = lib.gg_r1cs_solve(self.handle, ptr(wbuf), n_in, int(wdev), ptr(W), ptr(A), ptr(B), ptr(C),
                                int(on_device), ctypes.byref(bad))
-        if rc == GG_ERR_UNSATISFIED:
-            raise UnsatisfiedConstraintError(bad.value, lib.gg_last_error().decode())
-        check(rc)
+        self._raise_for(rc, bad)
         return Solution(W, A, B, C, nw, nc, on_device=on_device)
 
     def solve_resident(self, witness: bytes):
@@ -346,97 +365,40 @@ class R1CS:
             raise ValueError("invalid witness size, got %d bytes, expected %d" % (len(witness), 32 * n_in))
         bad = ctypes.c_int64(-1)
         rc = lib.gg_r1cs_solve(self.handle, ptr(witness), n_in, 0, None, None, None, None, 1, ctypes.byref(bad))
-        if rc == GG_ERR_UNSATISFIED:
-            raise UnsatisfiedConstraintError(bad.value, lib.gg_last_error().decode())
-        check(rc)
+        self._raise_for(rc, bad)
         p = [ctypes.c_void_p() for _ in range(4)]
         check(lib.gg_r1cs_solution_dev(self.handle, *(ctypes.byref(x) for x in p)))
         return Solution(p[0], p[1], p[2], p[3], self.n_wires, self.n_constraints, on_device=True)
 
-    def close(self):
-        if getattr(self, "handle", None):
-            lib.gg_r1cs_release(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def compute_scs_levels(nb_inputs: int, n_wires: int, wires) -> list:
-    """r1cs.Levels of a sparse R1CS (blueprint.go updateInstructionTree over
-    xa, xb, xc): wires < nb_inputs are the witness."""
-    level = np.full(n_wires, -1, dtype=np.int64)
-    w = np.asarray(wires, dtype=np.int64).reshape(-1, 3)
-    out = []
-    for c in range(len(w)):
-        mx, outs = -1, []
-        for x in w[c]:
-            x = int(x)
-            if x < nb_inputs:
-                continue
-            if level[x] < 0:
-                if x not in outs:
-                    outs.append(x)
-            elif level[x] > mx:
-                mx = int(level[x])
-        mx += 1
-        for x in outs:
-            level[x] = mx
-        while len(out) <= mx:
-            out.append([])
-        out[mx].append(c)
-    return out
-
-
-class SparseR1CS:
+class SparseR1CS(_System):
     """Device-resident sparse R1CS (gg_scs_create) with its solver: the PlonK
     side of r1cs.Solve (constraint/blueprint_scs.go:53-151), returning the
     L, R, O columns of evaluateLROSmallDomain (system.go:221-264)."""
+    _set_hints_fn, _schedule_fn, _release_fn = lib.gg_scs_set_hints, lib.gg_scs_schedule, lib.gg_scs_release
 
     def __init__(self, nb_public: int, nb_secret: int, n_wires: int, wires, qidx, coeffs: Sequence[int],
                  flags=None, levels=None, curve: str = "bls12-381", hints=None, hint_levels=None):
-        from ._lib import GG_CURVE_BN254, GG_CURVE_BLS12_381
-        self.curve = curve
-        self.mod = fr.BLS_R if curve == "bls12-381" else fr.R
-        self._mont = fr.bls_fr_mont if curve == "bls12-381" else fr.fr_mont
-        cid = GG_CURVE_BLS12_381 if curve == "bls12-381" else GG_CURVE_BN254
+        cid = self._field(curve, curve != "bls12-381")
         self.nb_public, self.nb_secret, self.n_wires = nb_public, nb_secret, n_wires
         self.wires = np.ascontiguousarray(wires, dtype=np.uint32)
         self.qidx = np.ascontiguousarray(qidx, dtype=np.uint32)
         self.n_constraints = len(self.wires) // 3
         self.flags = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
-        self.hints = list(hints) if hints else None
-        if self.hints and (levels is None or hint_levels is None):
-            levels, hint_levels = compute_scs_levels_with_hints(nb_public + nb_secret, n_wires, self.wires,
-                                                                self.hints)
-        if levels is None:
-            levels = compute_scs_levels(nb_public + nb_secret, n_wires, self.wires)
-        self.levels, self.hint_levels = levels, hint_levels
-        lo = np.zeros(len(levels) + 1, dtype=np.uint32)
-        lo[1:] = np.cumsum([len(x) for x in levels])
-        lc = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint32) for x in levels])
-                                  if levels else np.zeros(0, dtype=np.uint32), dtype=np.uint32)
-        cbytes = b"".join(self._mont(int(k) % self.mod) for k in coeffs)
+        lo, lc = self._set_levels(hints, levels, hint_levels, lambda hs: compute_scs_levels_with_hints(
+            nb_public + nb_secret, n_wires, self.wires, hs))
+        cbytes = self._coeff_bytes(coeffs)
         self.coeffs_mont = cbytes  # the coefficient table as uploaded (plonk_prover.setup reads it)
         h = ctypes.c_void_p()
         check(lib.gg_scs_create(cid, n_wires, self.n_constraints, nb_public, ptr(self.wires), ptr(self.qidx),
-                                ptr(self.flags), ptr(cbytes), len(coeffs), ptr(lo), ptr(lc), len(levels),
-                                ctypes.byref(h)))
+                                ptr(self.flags), ptr(cbytes), len(coeffs), ptr(lo), ptr(lc),
+                                len(self.levels), ctypes.byref(h)))
         self.handle = h
         check(lib.gg_scs_set_inputs(h, nb_public, nb_secret))
-        if self.hints:
-            index = {int(k) % self.mod: i for i, k in reversed(list(enumerate(coeffs)))}
-            self.set_hints(self.hints, hint_levels, lambda k: index[int(k) % self.mod])
+        self._set_own_hints(coeffs)
         d = ctypes.c_size_t()
         check(lib.gg_scs_info(h, None, None, ctypes.byref(d)))
         self.domain = d.value
-
-    def set_hints(self, hints, hint_levels, coeff_index):
-        """gg_scs_set_hints: once, before the first solve."""
-        _set_hints(lib.gg_scs_set_hints, self.handle, hints, hint_levels, coeff_index)
 
     @classmethod
     def from_constraints(cls, nb_public: int, nb_secret: int, n_wires: int, constraints, flags=None,
@@ -448,19 +410,11 @@ class SparseR1CS:
         wires, qidx = [], []
         for xa, xb, xc, *qs in constraints:
             wires += [xa, xb, xc]
-            for k in qs:
-                k %= mod
-                if k not in index:
-                    index[k] = len(table)
-                    table.append(k)
-                qidx.append(index[k])
+            qidx += [_intern(table, index, k % mod) for k in qs]
         for h in hints or ():
             for expr in h.inputs:
                 for _, k in expr:
-                    k %= mod
-                    if k not in index:
-                        index[k] = len(table)
-                        table.append(k)
+                    _intern(table, index, k % mod)
         return cls(nb_public, nb_secret, n_wires, wires, qidx, table, flags, levels, curve, hints, hint_levels)
 
     def solve(self, witness, on_device: bool = True):
@@ -477,22 +431,5 @@ class SparseR1CS:
         bad = ctypes.c_int64(-1)
         rc = lib.gg_scs_solve(self.handle, ptr(wbuf), n_in, 0, *(ptr(x) for x in out), int(on_device),
                               ctypes.byref(bad))
-        if rc == GG_ERR_UNSATISFIED:
-            raise UnsatisfiedConstraintError(bad.value, lib.gg_last_error().decode())
-        check(rc)
+        self._raise_for(rc, bad)
         return out
-
-    def schedule(self):
-        """(strands, launches, segments) of the last solve (gg_scs_schedule)."""
-        return _schedule(lib.gg_scs_schedule, self.handle)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            lib.gg_scs_release(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -104,6 +104,24 @@ def test_gpu_scs_solver_errors():
     sys_.close()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("levels_only", [False, True])
+@pytest.mark.parametrize("cons", [(2, 1, 0, 0, 1, 1, 0, 0), (0, 2, 1, 1, 0, 1, 0, 0), (0, 1, 2, 1, 1, 0, 0, 0)],
+                         ids=["xa", "xb", "xc"])
+def test_gpu_scs_solver_division_by_zero(cons, levels_only, monkeypatch):
+    """errDivideByZero at each position of the new wire (public x0, secret x1,
+    new wire 2): xa with qL + qM xb = 0, xb with qR + qM xa = 0, xc with
+    qO = 0, under both schedules."""
+    from gnark_amd import solver
+    monkeypatch.setenv("GG_SOLVER_LEVELS", "1" if levels_only else "0")
+    sys_ = solver.SparseR1CS.from_constraints(1, 1, 3, [cons])
+    with pytest.raises(solver.UnsatisfiedConstraintError) as e:
+        sys_.solve([5, 6])
+    assert e.value.cid == 0
+    assert "division by zero" in str(e.value)
+    sys_.close()
+
+
 def scs_mimc(nb_chains, rounds, mod):
     """MiMC-style chains as sparse R1CS (std/hash/mimc encryptPow5 through
     frontend/cs/scs: a = x + k_r (add gate), b = a a, c = b b, x' = c a), four

@@ -240,3 +240,53 @@ def test_gpu_solver_bls12_381(seed, zero):
     vals = lambda b: [fr.bls_fr_unmont(bytes(b)[i:i + 32]) for i in range(0, len(b), 32)]
     assert vals(gW) == W and vals(gA) == A and vals(gB) == B and vals(gC) == C
     sys_.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("curve", ["bn254", "bls12-381"])
+@pytest.mark.parametrize("levels_only", [False, True])
+def test_gpu_solver_zero_coefficient_on_unknown(levels_only, curve, monkeypatch):
+    """x * x = 0 * w with w the unknown: no division by the coefficient is
+    possible, which both kernels (levels and strands) report as a malformed
+    constraint, not as an unsatisfied one."""
+    from gnark_amd import solver, GnarkAmdError
+    monkeypatch.setenv("GG_SOLVER_LEVELS", "1" if levels_only else "0")
+    sys_ = solver.R1CS.from_terms(1, 1, 3, [([(1, 1)], [(1, 1)], [(2, 0)])], curve=curve)
+    with pytest.raises(GnarkAmdError) as e:
+        sys_.solve([5])
+    assert e.value.code == 1  # GG_ERR_INVALID_ARG
+    assert "constraint #0" in str(e.value) and "zero coefficient on the unknown" in str(e.value)
+    sys_.close()
+
+
+@pytest.mark.gpu
+def test_gpu_solver_replans_when_witness_length_changes(monkeypatch):
+    """One handle (no gg_r1cs_set_inputs), witnesses of different lengths: the
+    strand plan and the captured graph are rebuilt for each length.  Wires
+    0 = ONE, 1 = a, 2 = b, 3 = c with a a = b, b b = c: with [a] both constraints
+    solve a wire, with [a, b] the first one is a check."""
+    import ctypes
+    from gnark_amd import fr
+    from gnark_amd._lib import check, lib, ptr
+    monkeypatch.setenv("GG_SOLVER_LEVELS", "0")
+    u32 = lambda x: np.ascontiguousarray(x, dtype=np.uint32)
+    off, wire, cidx = u32(range(7)), u32([1, 1, 2, 2, 2, 3]), u32([0] * 6)
+    lo, lc = u32([0, 1, 2]), u32([0, 1])
+    h = ctypes.c_void_p()
+    check(lib.gg_r1cs_create_ex(0, 4, 2, ptr(off), ptr(wire), ptr(cidx), ptr(fr.fr_mont(1)), 1, ptr(lo), ptr(lc), 2,
+                                ctypes.byref(h)))
+
+    def solve(vals):
+        wb = b"".join(fr.fr_mont(v) for v in vals)
+        W, bad = bytearray(4 * 32), ctypes.c_int64(-2)
+        rc = lib.gg_r1cs_solve(h, ptr(wb), len(vals), 0, ptr(W), None, None, None, 0, ctypes.byref(bad))
+        s = ctypes.c_int()
+        check(lib.gg_r1cs_schedule(h, ctypes.byref(s), None, None))
+        return rc, bad.value, _fr_list(W), s.value
+
+    assert solve([3]) == (0, -1, [1, 3, 9, 81], 1)
+    assert solve([3, 9]) == (0, -1, [1, 3, 9, 81], 1)
+    rc, bad, _, _ = solve([3, 10])
+    assert (rc, bad) == (6, 0)  # GG_ERR_UNSATISFIED at constraint 0
+    assert solve([3])[:3] == (0, -1, [1, 3, 9, 81])
+    check(lib.gg_r1cs_release(h))
