@@ -22,6 +22,7 @@
 // Every argument is validated on the host before the first device call.
 #include "common.h"
 #include "pairing.cuh"
+#include "pairing_host.h"
 #include "comb.h"
 #include "sha256.h"
 #include <algorithm>
@@ -273,8 +274,8 @@ static void fe_to_be(const F& mont, uint8_t out[32]) {
     const F c = from_mont(mont);
     for (int i = 0; i < 32; i++) out[i] = (uint8_t)(c.v[7 - i / 4] >> (8 * (3 - i % 4)));
 }
-// RFC 9380 5.3.1 expand_message_xmd, SHA-256, 48 bytes
-static Fr hash_to_field(const uint8_t* msg, size_t len, const uint8_t* dst, size_t dst_len) {
+// RFC 9380 5.3.1 expand_message_xmd, SHA-256, 48 bytes (pairing_host.h)
+Fr hash_to_field(const uint8_t* msg, size_t len, const uint8_t* dst, size_t dst_len) {
     const uint8_t dl = (uint8_t)dst_len;
     uint8_t b0[32], bi[32], out[64];
     {

@@ -36,6 +36,7 @@ GG_VERIFY_OK, GG_VERIFY_SUBGROUP, GG_VERIFY_PEDERSEN, GG_VERIFY_PAIRING = 0, 1, 
 GG_POINT_OK, GG_POINT_NOT_ON_CURVE, GG_POINT_NOT_IN_SUBGROUP = 0, 1, 2
 GG_GT_BYTES = 384
 GG_VERIFY_MAX_K = 1024
+GG_PLONK_VERIFY_OK, GG_PLONK_VERIFY_MALFORMED, GG_PLONK_VERIFY_QUOTIENT, GG_PLONK_VERIFY_KZG = 0, 1, 2, 3
 GG_PLONK_SETUP_TIMING_SLOTS = 10
 
 
@@ -236,6 +237,12 @@ def _load():
         "gg_groth16_vk_create": ([I, P, P, P, P, P, S, S, P, P, P, P, I, PP], I),
         "gg_groth16_vk_destroy": ([P], I),
         "gg_groth16_verify_batch": ([P, S, P, P, P, P, P], I),
+        "gg_plonk_vk_create": ([I, ctypes.c_uint64, P, P, P, P, P, I, P, S, P, P, PP], I),
+        "gg_plonk_vk_destroy": ([P], I),
+        "gg_plonk_verify_batch": ([P, S, P, P, HASH_FN, P, HASH_FN, P, P], I),
+        "gg_plonk_verify_batch_host": ([P, S, P, P, HASH_FN, P, HASH_FN, P, P], I),
+        "gg_kzg_verify_bn254": ([S, P, P, P, P, P, P, P], I),
+        "gg_kzg_verify_bn254_host": ([S, P, P, P, P, P, P, P], I),
         "gg_profile_enable": ([I], I),
         "gg_profile_get": ([ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),
                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)], I),
@@ -309,6 +316,8 @@ EXPORTED = [
     "gg_plonk_setup_timings", "gg_plonk_setup_pk", "gg_plonk_setup_release",
     "gg_pairing_bn254", "gg_pairing_check_bn254", "gg_pairing_bn254_host", "gg_g1_check_bn254", "gg_g2_check_bn254",
     "gg_hash_to_field_bn254", "gg_groth16_vk_create", "gg_groth16_vk_destroy", "gg_groth16_verify_batch",
+    "gg_plonk_vk_create", "gg_plonk_vk_destroy", "gg_plonk_verify_batch", "gg_plonk_verify_batch_host",
+    "gg_kzg_verify_bn254", "gg_kzg_verify_bn254_host",
 ]
 
 

@@ -1135,6 +1135,64 @@ int gg_groth16_vk_destroy(gg_groth16_vk_t vk);
 int gg_groth16_verify_batch(gg_groth16_vk_t vk, size_t n, const void *proofs, const void *commitments,
                             const void *poks, const void *public_witness, uint8_t *status_out);
 
+/* ------------------------------------------------- PlonK Verify, KZG openings
+ * plonk.Verify (backend/plonk/bn254/verify.go:45-294) for batches of BN254
+ * proofs under one verifying key, and kzg.Verify for batches of openings.
+ *
+ * The verifying key (setup.go:37-60 with vk.Kzg): size = vk.Size (a power of
+ * two >= 2); generator, coset_shift: fr Montgomery; S: 3 G1Affine; Q: Ql Qr Qm
+ * Qo Qk; Qcp: n_cmt G1Affine; commitment_indexes[n_cmt] =
+ * vk.CommitmentConstraintIndexes (both NULL when n_cmt == 0); nb_public: public
+ * inputs (PlonK has no ONE wire); kzg_g1 = vk.Kzg.G1, kzg_g2 = vk.Kzg.G2:
+ * G2 and [tau]G2.  Host pointers.  Makes no device call: validates, keeps a host
+ * copy and precomputes the line coefficients of G2 and [tau]G2; the first
+ * gg_plonk_verify_batch on the key uploads them.
+ * GG_ERR_INVALID_ARG, the message naming the offender: a null pointer, size not
+ * a power of two >= 2, n_cmt < 0, a commitment index with nb_public + index >=
+ * size, a key point off the curve, a G2 point at infinity, off the twist or
+ * outside the r-torsion.  GG_ERR_UNSUPPORTED: curve != GG_CURVE_BN254. */
+typedef struct gg_plonk_vk *gg_plonk_vk_t;
+int gg_plonk_vk_create(int curve, uint64_t size, const void *generator, const void *coset_shift, const void *S,
+                       const void *Q, const void *Qcp, int n_cmt, const uint32_t *commitment_indexes,
+                       size_t nb_public, const void *kzg_g1, const void *kzg_g2, gg_plonk_vk_t *out);
+int gg_plonk_vk_destroy(gg_plonk_vk_t vk);
+/* status of one proof, in the order verify.go decides them */
+#define GG_PLONK_VERIFY_OK 0
+#define GG_PLONK_VERIFY_MALFORMED 1 /* a proof point off the curve, or an fr of the proof / witness >= r */
+#define GG_PLONK_VERIFY_QUOTIENT 2  /* verify.go:193 errWrongClaimedQuotient */
+#define GG_PLONK_VERIFY_KZG 3       /* verify.go:276 BatchVerifyMultiPoints */
+/* plonk.Verify of n proofs under one key; every proof gets its own verdict, the
+ * same one every time.  proofs: n x gg_plonk_proof_size_ex(GG_CURVE_BN254,
+ * n_cmt) bytes in the layout gg_plonk_prove writes; public_witness: n x
+ * nb_public fr Montgomery (NULL when nb_public == 0); challenge_hash /
+ * folding_hash (+ ctx): the verifier's ChallengeHash / KZGFoldingHash, NULL =
+ * SHA-256; status_out: n uint8.  Host pointers.  The transcripts and the BSB22
+ * hashes run on the host; the point checks, PI(zeta), the quotient identity,
+ * every G1 combination and the pairing check on the device.  The two openings
+ * are checked in one product e(A, G2) e(B, [tau]G2) == 1 with the coefficient
+ *   lambda = SHA-256("gg-plonk-kzg-lambda" | gamma_kzg (32 B big-endian) |
+ *            RawBytes(BatchedProof.H) | RawBytes(ZShiftedOpening.H)) mod r, 0 -> 1
+ * (gnark-crypto draws it at random).  One batch at a time per key.
+ * Returns GG_OK whenever the batch ran, whatever the verdicts;
+ * GG_ERR_INVALID_ARG (before any device call): vk NULL, n == 0, a null array. */
+int gg_plonk_verify_batch(gg_plonk_vk_t vk, size_t n, const void *proofs, const void *public_witness,
+                          gg_hash_fn challenge_hash, void *challenge_ctx, gg_hash_fn folding_hash, void *folding_ctx,
+                          uint8_t *status_out);
+/* the same per-proof functions in a loop on the calling host thread (no device call) */
+int gg_plonk_verify_batch_host(gg_plonk_vk_t vk, size_t n, const void *proofs, const void *public_witness,
+                               gg_hash_fn challenge_hash, void *challenge_ctx, gg_hash_fn folding_hash,
+                               void *folding_ctx, uint8_t *status_out);
+/* kzg.Verify of n independent openings under one SRS: ok_out[i] (uint8) = 1 iff
+ * e(C_i - y_i G + z_i H_i, G2) e(-H_i, [tau]G2) == 1.  kzg_g1: G (G1Affine);
+ * kzg_g2: G2, [tau]G2; digests C, quotients H: n G1Affine; points z, values y:
+ * n fr Montgomery.  Host pointers.  Exact for y = 0, z = 0 and H = infinity; an
+ * off-curve C_i or H_i or a scalar >= r gives ok = 0.  Runs the kernels of the
+ * PlonK path; _host: the same functions on the calling thread. */
+int gg_kzg_verify_bn254(size_t n, const void *kzg_g1, const void *kzg_g2, const void *digests, const void *quotients,
+                        const void *points, const void *values, uint8_t *ok_out);
+int gg_kzg_verify_bn254_host(size_t n, const void *kzg_g1, const void *kzg_g2, const void *digests,
+                             const void *quotients, const void *points, const void *values, uint8_t *ok_out);
+
 /* ------------------------------------------------------------ profiling
  * Kernel-level timing with HIP events recorded on the stream each kernel is
  * launched on (bench.py uses it for the roofline of the dominant kernel).
