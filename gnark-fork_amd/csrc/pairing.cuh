@@ -213,6 +213,18 @@ struct Bls12381Tower {
     {0x000cfff3u, 0xaa270000u, 0xfc34000au, 0x53cc0032u, 0x6b0a807fu, 0x478fe97au, 0xe6ba24d7u, 0xb1d37ebeu,
      0xbf78ab2fu, 0x8ec9733bu, 0x3d83de7eu, 0x09d64551u, 0x000cfff3u, 0xaa270000u, 0xfc34000au, 0x53cc0032u,
      0x6b0a807fu, 0x478fe97au, 0xe6ba24d7u, 0xb1d37ebeu, 0xbf78ab2fu, 0x8ec9733bu, 0x3d83de7eu, 0x09d64551u};
+    // phi(x, y) = (BETA x, y): [x^2] phi(P) + P = 0 on G1
+    static constexpr uint32_t BETA[12] =
+    {0x8671f071u, 0xcd03c9e4u, 0x1fcda5d2u, 0x5dab2246u, 0xd3851b95u, 0x587042afu, 0x01bacb9eu, 0x8eb60ebeu,
+     0x83d050d2u, 0x03f97d6eu, 0x54638741u, 0x18f02065u};
+    // psi(x, y) = (conj(x) PSI[0], conj(y) PSI[1]): psi(Q) = [x] Q on G2
+    static constexpr uint32_t PSI[2][24] = {
+    {0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u,
+     0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x867545c3u, 0x890dc9e4u, 0x3285a5d5u, 0x2af32253u,
+     0x309b7e2cu, 0x50880866u, 0x7e881024u, 0xa20d1b8cu, 0xe2db9068u, 0x14e4f04fu, 0x1564853au, 0x14e56d3fu},
+    {0xa55c9ad1u, 0x3e2f585du, 0x86c18183u, 0x4294213du, 0x8b623732u, 0x382844c8u, 0x19103e18u, 0x92ad2afdu,
+     0xac7cf0b9u, 0x1d794e4fu, 0x7d825ec8u, 0x0bd592fcu, 0x5aa30fdau, 0x7bcfa7a2u, 0x2a927e7cu, 0xdc17dec1u,
+     0x6b4ebef1u, 0x2f088dd8u, 0xda74d4a7u, 0xd1ca2087u, 0x96cebc1du, 0x2da25966u, 0xbbfd87d2u, 0x0e2b7eedu}};
     template <int K, int I>
     static GG_HD F2 gamma() {
         F2 r;
@@ -229,6 +241,22 @@ struct Bls12381Tower {
         for (int i = 0; i < NL; i++) {
             r.a0.v[i] = BT[i];
             r.a1.v[i] = BT[NL + i];
+        }
+        return r;
+    }
+    static GG_HD F endo_beta() {
+        F r;
+#pragma unroll
+        for (int i = 0; i < NL; i++) r.v[i] = BETA[i];
+        return r;
+    }
+    template <int I>
+    static GG_HD F2 endo_psi() {
+        F2 r;
+#pragma unroll
+        for (int i = 0; i < NL; i++) {
+            r.a0.v[i] = PSI[I][i];
+            r.a1.v[i] = PSI[I][NL + i];
         }
         return r;
     }
@@ -689,6 +717,52 @@ GG_HD int g1_check(const Affine<typename Tw::F>& p) {
     if (!(sqr(p.y) == sqr(p.x) * p.x + Tw::b_g1())) return 1;
     if constexpr (Tw::G1_COFACTOR_ONE) return 0;
     else return times_r_is_inf<Tw, typename Tw::F>(p) ? 0 : 2;
+}
+
+// ---------------------------------------------------------------- endomorphism checks
+// The same answers as g1_check / g2_check from one or two multiplications by
+// |x| (64 bits, weight 6) instead of the 255-bit one by r (gnark-crypto's
+// IsInSubGroup; Scott, "A note on group membership tests", 2021):
+//   G1: [x^2] phi(P) + P = 0, phi(x, y) = (beta x, y) acting as x^2 - 1 on G1;
+//   G2: psi(Q) = [x] Q, x < 0, so psi(Q) + [|x|] Q = 0.
+// The point loops run over Called<FF> as times_r_is_inf does.
+template <class Tw, class FF>
+GG_HDN Jac<Called<FF>> mul_x_abs(const Jac<Called<FF>>& a) {
+    Jac<Called<FF>> acc = a;
+    for (int i = Tw::X_TOP - 1; i >= 0; i--) {
+        acc = jac_dbl(acc);
+        if ((Tw::X >> i) & 1) acc = jac_add(acc, a);
+    }
+    return acc;
+}
+template <class Tw>
+GG_HDN bool g1_endo_is_member(const Affine<typename Tw::F>& p) {
+    using C = Called<typename Tw::F>;
+    Jac<C> a{C{p.x} * C{Tw::endo_beta()}, C{p.y}, C::one()};
+    a = mul_x_abs<Tw, typename Tw::F>(a);
+    a = mul_x_abs<Tw, typename Tw::F>(a);
+    return jac_add(a, Jac<C>{C{p.x}, C{p.y}, C::one()}).is_inf();
+}
+template <class Tw>
+GG_HDN bool g2_endo_is_member(const Affine<typename Tw::F2>& q) {
+    using C = Called<typename Tw::F2>;
+    const Jac<C> base{C{q.x}, C{q.y}, C::one()};
+    const Jac<C> a = mul_x_abs<Tw, typename Tw::F2>(base);
+    const Jac<C> psi{C{Tw::conj(q.x)} * C{Tw::template endo_psi<0>()}, C{Tw::conj(q.y)} * C{Tw::template endo_psi<1>()},
+                     C::one()};
+    return jac_add(a, psi).is_inf();
+}
+template <class Tw>
+GG_HD int g1_check_endo(const Affine<typename Tw::F>& p) {
+    if (p.is_inf()) return 0;
+    if (!(sqr(p.y) == sqr(p.x) * p.x + Tw::b_g1())) return 1;
+    return g1_endo_is_member<Tw>(p) ? 0 : 2;
+}
+template <class Tw>
+GG_HD int g2_check_endo(const Affine<typename Tw::F2>& q) {
+    if (q.is_inf()) return 0;
+    if (!(sqr(q.y) == sqr(q.x) * q.x + Tw::b_twist())) return 1;
+    return g2_endo_is_member<Tw>(q) ? 0 : 2;
 }
 
 }  // namespace pairing

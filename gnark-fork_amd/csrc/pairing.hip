@@ -232,9 +232,9 @@ static void fe_to_be(const F& mont, uint8_t out[32]) {
     for (int i = 0; i < 32; i++) out[i] = (uint8_t)(c.v[7 - i / 4] >> (8 * (3 - i % 4)));
 }
 // RFC 9380 5.3.1 expand_message_xmd, SHA-256, 48 bytes (pairing_host.h)
-Fr hash_to_field(const uint8_t* msg, size_t len, const uint8_t* dst, size_t dst_len) {
+void expand_message_xmd48(const uint8_t* msg, size_t len, const uint8_t* dst, size_t dst_len, uint8_t out[64]) {
     const uint8_t dl = (uint8_t)dst_len;
-    uint8_t b0[32], bi[32], out[64];
+    uint8_t b0[32], bi[32];
     {
         const uint8_t zpad[64] = {0};
         const uint8_t tail[3] = {0, 48, 0};  // l_i_b_str (2 bytes), then I2OSP(0, 1)
@@ -258,6 +258,10 @@ Fr hash_to_field(const uint8_t* msg, size_t len, const uint8_t* dst, size_t dst_
         h.final(bi);
         memcpy(out + 32 * (i - 1), bi, 32);
     }
+}
+Fr hash_to_field(const uint8_t* msg, size_t len, const uint8_t* dst, size_t dst_len) {
+    uint8_t out[64];
+    expand_message_xmd48(msg, len, dst, dst_len, out);
     return fr_from_be(out, 48);
 }
 static const uint8_t kCommitmentDst[] = "bsb22-commitment";  // constraint/commitment.go:7

@@ -244,6 +244,13 @@ def _load():
         "gg_groth16_vk_create": ([I, P, P, P, P, P, S, S, P, P, P, P, I, PP], I),
         "gg_groth16_vk_destroy": ([P], I),
         "gg_groth16_verify_batch": ([P, S, P, P, P, P, P], I),
+        "gg_groth16_vk_create_bls12_381": ([P, P, P, P, P, S, S, P, P, P, P, I, PP], I),
+        "gg_groth16_vk_destroy_bls12_381": ([P], I),
+        "gg_groth16_verify_batch_bls12_381": ([P, S, P, P, P, P, P], I),
+        "gg_groth16_verify_batch_bls12_381_host": ([P, S, P, P, P, P, P], I),
+        "gg_hash_to_field_bls12_381": ([P, S, P, S, P], I),
+        "gg_g1_check_endo_bls12_381": ([S, P, P], I),
+        "gg_g2_check_endo_bls12_381": ([S, P, P], I),
         "gg_plonk_vk_create": ([I, ctypes.c_uint64, P, P, P, P, P, I, P, S, P, P, PP], I),
         "gg_plonk_vk_destroy": ([P], I),
         "gg_plonk_verify_batch": ([P, S, P, P, HASH_FN, P, HASH_FN, P, P], I),
@@ -327,6 +334,9 @@ EXPORTED = [
     "gg_kzg_verify_bn254", "gg_kzg_verify_bn254_host",
     "gg_pairing_bls12_381", "gg_pairing_check_bls12_381", "gg_pairing_bls12_381_host",
     "gg_pairing_bls12_381_table_host", "gg_g1_check_bls12_381", "gg_g2_check_bls12_381",
+    "gg_groth16_vk_create_bls12_381", "gg_groth16_vk_destroy_bls12_381", "gg_groth16_verify_batch_bls12_381",
+    "gg_groth16_verify_batch_bls12_381_host", "gg_hash_to_field_bls12_381", "gg_g1_check_endo_bls12_381",
+    "gg_g2_check_endo_bls12_381",
 ]
 
 

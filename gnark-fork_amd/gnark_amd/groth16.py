@@ -1010,42 +1010,90 @@ class VerifyingKey:
             pass
 
 
-def _witness_bytes(w) -> bytes:
+class Bls12381VerifyingKey:
+    """Verifying key over BLS12-381 (gg_groth16_vk_create_bls12_381).  Creation
+    runs on the host alone: -gamma and -delta, the fixed operands' line tables
+    and e(alpha, beta)^3.  The first verify_batch on the GPU uploads the key and
+    builds the window table of K[1:]; verify_batch(..., host=True) needs no GPU."""
+    curve = "bls12-381"
+
+    def __init__(self, data: VerifyingKeyData):
+        if data.curve != "bls12-381":
+            raise ValueError(f"Bls12381VerifyingKey takes a 'bls12-381' key, got {data.curve!r}")
+        self.data = data
+        committed = [list(c) for c in data.public_and_commitment_committed]
+        nc = len(committed)
+        self.n_commitments, self.nb_public = nc, data.nb_public
+        off = np.zeros(nc + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(c) for c in committed])
+        idx = np.ascontiguousarray([i for c in committed for i in c], dtype=np.uint32)
+        h = ctypes.c_void_p()
+        check(lib.gg_groth16_vk_create_bls12_381(
+            ptr(data.alpha1), ptr(data.beta2), ptr(data.gamma2), ptr(data.delta2), ptr(data.K),
+            len(data.K) // 96, data.nb_public, ptr(data.commitment_key_g) if nc else None,
+            ptr(data.commitment_key_g_root_sigma_neg) if nc else None, ptr(off) if nc else None,
+            ptr(idx) if len(idx) else None, nc, ctypes.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib.gg_groth16_vk_destroy_bls12_381(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _witness_bytes(w, mont=fr.fr_mont) -> bytes:
     """fr Montgomery bytes of a public witness given as bytes or as integers."""
     if isinstance(w, (bytes, bytearray, memoryview)):
         return bytes(w)
     if hasattr(w, "tobytes"):
         return w.tobytes()
-    return b"".join(fr.fr_mont(int(x)) for x in w)
+    return b"".join(mont(int(x)) for x in w)
 
 
-def verify_batch(proofs: Sequence[Proof], vk: VerifyingKey, witnesses: Sequence) -> list:
-    """groth16.Verify of every (proof, public witness) pair under vk: a list of
-    VERIFY_* statuses, one deterministic verdict per proof.  A witness is the
-    public inputs without the ONE wire, as fr Montgomery bytes or as integers."""
+def verify_batch(proofs: Sequence[Proof], vk, witnesses: Sequence, host: bool = False) -> list:
+    """groth16.Verify of every (proof, public witness) pair under vk (a
+    VerifyingKey or a Bls12381VerifyingKey): a list of VERIFY_* statuses, one
+    deterministic verdict per proof.  A witness is the public inputs without the
+    ONE wire, as fr Montgomery bytes of the key's curve or as integers.
+    host=True (BLS12-381 keys only) runs the same code on the calling thread."""
+    bls = isinstance(vk, Bls12381VerifyingKey)
+    if host and not bls:
+        raise ValueError("host=True: the host verifier exists for a Bls12381VerifyingKey only")
     n = len(proofs)
     if n != len(witnesses):
         raise ValueError(f"{n} proofs, {len(witnesses)} witnesses")
     nc, nw = vk.n_commitments, vk.nb_public - 1
-    wb = [_witness_bytes(w) for w in witnesses]
+    g1b, g2b = _SIZES["bls12-381" if bls else "bn254"][:2]
+    wb = [_witness_bytes(w, fr.bls_fr_mont if bls else fr.fr_mont) for w in witnesses]
     for i, (p, w) in enumerate(zip(proofs, wb)):
         if len(w) != 32 * nw:
             raise ValueError(f"invalid witness size, got {len(w) // 32}, expected {nw} (public - ONE_WIRE)")
         if len(p.Commitments) != nc:
             raise ValueError(f"proof {i}: {len(p.Commitments)} commitments, the key has {nc}")
+        if bls and (len(p.Ar) != g1b or len(p.Bs) != g2b or len(p.Krs) != g1b or
+                    any(len(c) != g1b for c in p.Commitments) or (nc and len(p.CommitmentPok) != g1b)):
+            raise ValueError(f"proof {i}: its points are not {g1b}-byte G1 / {g2b}-byte G2 points of the key's curve")
     packed = b"".join(p.Ar + p.Bs + p.Krs for p in proofs)
     cm = b"".join(b"".join(p.Commitments) for p in proofs)
     pok = b"".join(p.CommitmentPok for p in proofs)
     wit = b"".join(wb)
     status = bytearray(n)
-    check(lib.gg_groth16_verify_batch(vk.handle, n, ptr(packed), ptr(cm) if nc else None, ptr(pok) if nc else None,
-                                      ptr(wit) if nw else None, ptr(status)))
+    fn = lib.gg_groth16_verify_batch if not bls else (
+        lib.gg_groth16_verify_batch_bls12_381_host if host else lib.gg_groth16_verify_batch_bls12_381)
+    check(fn(vk.handle, n, ptr(packed), ptr(cm) if nc else None, ptr(pok) if nc else None,
+             ptr(wit) if nw else None, ptr(status)))
     return list(status)
 
 
-def verify(proof: Proof, vk: VerifyingKey, public_witness) -> None:
+def verify(proof: Proof, vk, public_witness, host: bool = False) -> None:
     """groth16.Verify (verify.go:43-140): returns None for a valid proof, raises
     VerifyError with gnark's message otherwise."""
-    st = verify_batch([proof], vk, [public_witness])[0]
+    st = verify_batch([proof], vk, [public_witness], host=host)[0]
     if st != VERIFY_OK:
         raise VerifyError(st)

@@ -29,6 +29,10 @@ class _Curve:
         self.pairing_check = getattr(lib, "gg_pairing_check_" + suffix)
         self.g1_check = getattr(lib, "gg_g1_check_" + suffix)
         self.g2_check = getattr(lib, "gg_g2_check_" + suffix)
+        # the endomorphism checks exist where G1 has a cofactor (BLS12-381)
+        self.g1_check_endo = getattr(lib, "gg_g1_check_endo_" + suffix, None)
+        self.g2_check_endo = getattr(lib, "gg_g2_check_endo_" + suffix, None)
+        self.hash_to_field = getattr(lib, "gg_hash_to_field_" + suffix)
 
 
 _CURVES = {}
@@ -77,28 +81,39 @@ def pairing_check(g1: bytes, g2: bytes, k: int, curve: str = "bn254") -> list:
     return [bool(x) for x in ok]
 
 
-def g1_check(points: bytes, curve: str = "bn254") -> list:
+def _check_fn(c: _Curve, which: str, endo: bool, curve: str):
+    if not endo:
+        return getattr(c, which)
+    fn = getattr(c, which + "_endo")
+    if fn is None:
+        raise ValueError(f"endo=True: the endomorphism checks exist over 'bls12-381' only, not over {curve!r}")
+    return fn
+
+
+def g1_check(points: bytes, curve: str = "bn254", endo: bool = False) -> list:
     """One flag per G1Affine: 0 good, 1 not on the curve, 2 not in the subgroup
-    of order r (BN254 has cofactor 1: never 2 there)."""
+    of order r (BN254 has cofactor 1: never 2 there).  endo=True (BLS12-381):
+    the same flags by [x^2] phi(P) + P = 0 instead of the multiplication by r."""
     c = _curve(curve)
     n = _count(points, c.g1, "g1")
     f = bytearray(n)
-    check(c.g1_check(n, ptr(points), ptr(f)))
+    check(_check_fn(c, "g1_check", endo, curve)(n, ptr(points), ptr(f)))
     return list(f)
 
 
-def g2_check(points: bytes, curve: str = "bn254") -> list:
-    """One flag per G2Affine: 0 good, 1 not on the twist, 2 not in the r-torsion."""
+def g2_check(points: bytes, curve: str = "bn254", endo: bool = False) -> list:
+    """One flag per G2Affine: 0 good, 1 not on the twist, 2 not in the r-torsion.
+    endo=True (BLS12-381): the same flags by psi(Q) = [x] Q."""
     c = _curve(curve)
     n = _count(points, c.g2, "g2")
     f = bytearray(n)
-    check(c.g2_check(n, ptr(points), ptr(f)))
+    check(_check_fn(c, "g2_check", endo, curve)(n, ptr(points), ptr(f)))
     return list(f)
 
 
-def hash_to_field(msg: bytes, dst: bytes = b"bsb22-commitment") -> bytes:
-    """fr.Hash(msg, dst, 1): one fr in Montgomery form (32 bytes)."""
+def hash_to_field(msg: bytes, dst: bytes = b"bsb22-commitment", curve: str = "bn254") -> bytes:
+    """fr.Hash(msg, dst, 1): one fr of the curve's scalar field in Montgomery form (32 bytes)."""
     out = bytearray(32)
-    check(lib.gg_hash_to_field_bn254(ptr(msg) if msg else None, len(msg), ptr(dst) if dst else None, len(dst),
-                                     ptr(out)))
+    check(_curve(curve).hash_to_field(ptr(msg) if msg else None, len(msg), ptr(dst) if dst else None, len(dst),
+                                      ptr(out)))
     return bytes(out)

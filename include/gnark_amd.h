@@ -1161,6 +1161,52 @@ int gg_groth16_vk_destroy(gg_groth16_vk_t vk);
 int gg_groth16_verify_batch(gg_groth16_vk_t vk, size_t n, const void *proofs, const void *commitments,
                             const void *poks, const void *public_witness, uint8_t *status_out);
 
+/* groth16.Verify over BLS12-381 (backend/groth16/bls12-381/verify.go:42-140),
+ * BSB22 commitments included: its own handle type and entry points.  The
+ * contracts are those of gg_groth16_vk_create / gg_groth16_verify_batch above,
+ * argument for argument (without the curve argument), with these sizes:
+ * G1Affine 96 B, G2Affine 192 B, a proof 384 B (Ar | Bs | Krs), fr 32 B in
+ * Montgomery form over the BLS12-381 scalar field.  The same GG_VERIFY_*
+ * statuses in verify.go's order, the same refusals before any work with the
+ * message naming the offender, GG_VERIFY_MAX_K; an all-zero point is the
+ * infinity and contributes the factor 1.  The commitment hash is
+ * fr.Hash(Marshal(C_j) | committed public values, "bsb22-commitment") with
+ * Marshal the 96-B uncompressed encoding (x | y big-endian, 0x40 then zeros for
+ * the infinity) and 32-B big-endian values; the folding challenge is
+ * sha256("r" | hashes) mod r for two or more commitments.
+ * G1 has a cofactor here: Ar, Krs, every commitment and the PoK get the curve
+ * equation and a subgroup test, as Bs does (gg_g1_check_endo_bls12_381 /
+ * gg_g2_check_endo_bls12_381 below are those tests).
+ * gg_groth16_vk_create_bls12_381 makes NO device call: it validates, keeps a
+ * host copy, negates gamma and delta, precomputes the 68-line tables of
+ * -delta, -gamma, G and GRootSigmaNeg and e(alpha, beta)^3 on the calling
+ * thread.  The first gg_groth16_verify_batch_bls12_381 on the key uploads it
+ * and builds the window table of K[1:] on the current device; one batch at a
+ * time per key, bounded waits.  _host: the same per-proof functions in a loop
+ * on the calling thread (no device call; host pointers; the public-input sum by
+ * plain scalar multiplication), so a key works where there is no GPU. */
+typedef struct gg_groth16_vk_bls *gg_groth16_vk_bls_t;
+int gg_groth16_vk_create_bls12_381(const void *alpha1, const void *beta2, const void *gamma2, const void *delta2,
+                                   const void *K, size_t n_K, size_t nb_public, const void *ped_g,
+                                   const void *ped_g_root_sigma_neg, const uint32_t *committed_off,
+                                   const uint32_t *committed_idx, int n_commitments, gg_groth16_vk_bls_t *out);
+int gg_groth16_vk_destroy_bls12_381(gg_groth16_vk_bls_t vk);
+int gg_groth16_verify_batch_bls12_381(gg_groth16_vk_bls_t vk, size_t n, const void *proofs, const void *commitments,
+                                      const void *poks, const void *public_witness, uint8_t *status_out);
+int gg_groth16_verify_batch_bls12_381_host(gg_groth16_vk_bls_t vk, size_t n, const void *proofs,
+                                           const void *commitments, const void *poks, const void *public_witness,
+                                           uint8_t *status_out);
+/* gg_hash_to_field_bn254 over the BLS12-381 scalar field */
+int gg_hash_to_field_bls12_381(const void *msg, size_t len, const void *dst, size_t dst_len, void *out32);
+/* The flags of gg_g1_check_bls12_381 / gg_g2_check_bls12_381 (0 / 1 / 2, the
+ * infinity good), the same answer on every input, by the endomorphism tests of
+ * gnark-crypto's IsInSubGroup instead of the multiplication by r:
+ * G1: [x^2] phi(P) + P = infinity, phi(x, y) = (beta x, y);
+ * G2: psi(Q) = [x] Q, psi the untwist-Frobenius-twist map.  One or two
+ * multiplications by the 64-bit |x| of weight 6. */
+int gg_g1_check_endo_bls12_381(size_t n, const void *g1, uint8_t *flags_out);
+int gg_g2_check_endo_bls12_381(size_t n, const void *g2, uint8_t *flags_out);
+
 /* ------------------------------------------------- PlonK Verify, KZG openings
  * plonk.Verify (backend/plonk/bn254/verify.go:45-294) for batches of BN254
  * proofs under one verifying key, and kzg.Verify for batches of openings.
