@@ -61,20 +61,6 @@ static_assert(sizeof(ProofB) == 384, "proof layout");
 
 GG_HD G1C to_c(const G1B& a) { return G1C{CF{a.x}, CF{a.y}}; }
 
-// a^(p - 2) with the products as calls (p - 2 differs from p in the lowest limb only)
-GG_HDN FpBls inv_call(const FpBls& a) {
-    const CF b{a};
-    CF acc = CF::one();
-#pragma unroll
-    for (int w = FpBlsCfg::N - 1; w >= 0; w--) {
-        const uint32_t word = w == 0 ? FpBlsCfg::P[0] - 2u : FpBlsCfg::P[w];
-        for (int i = 31; i >= 0; i--) {
-            acc = sqr(acc);
-            if ((word >> i) & 1) acc = acc * b;
-        }
-    }
-    return acc.v;
-}
 GG_HDN G1B xyzz_to_affine_c(const XyzzC& p) {
     if (p.is_inf()) return G1B::inf();
     const CF i3{inv_call(p.zzz.v)};
@@ -259,29 +245,12 @@ __global__ void __launch_bounds__(64) k_g2_check_endo_bls(size_t n, const G2B* q
 }
 
 // ------------------------------------------------------------------ host side
-// big-endian bytes mod r, Montgomery form (Horner over the bytes)
-static FrBls frb_from_be(const uint8_t* b, size_t n) {
-    FrBls m256 = FrBls::zero(), acc = FrBls::zero();
-    m256.v[0] = 256;
-    m256 = to_mont(m256);
-    for (size_t i = 0; i < n; i++) {
-        FrBls d = FrBls::zero();
-        d.v[0] = b[i];
-        acc = acc * m256 + to_mont(d);
-    }
-    return acc;
-}
 // the canonical value, big-endian, 4 bytes per limb
 template <class F>
 static void fe_to_be(const F& mont, uint8_t* out) {
     constexpr int N = sizeof(F) / 4;
     const F c = from_mont(mont);
     for (int i = 0; i < 4 * N; i++) out[i] = (uint8_t)(c.v[N - 1 - i / 4] >> (8 * (3 - i % 4)));
-}
-static FrBls hash_to_field_bls(const uint8_t* msg, size_t len, const uint8_t* dst, size_t dst_len) {
-    uint8_t out[64];
-    expand_message_xmd48(msg, len, dst, dst_len, out);
-    return frb_from_be(out, 48);
 }
 static const uint8_t kCommitmentDstB[] = "bsb22-commitment";  // constraint/commitment.go:7
 

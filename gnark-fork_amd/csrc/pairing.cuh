@@ -680,6 +680,10 @@ GG_HD Called<FF> operator-(const Called<FF>& a, const Called<FF>& b) {
     return Called<FF>{a.v - b.v};
 }
 template <class FF>
+GG_HD Called<FF> operator-(const Called<FF>& a) {
+    return Called<FF>{-a.v};
+}
+template <class FF>
 GG_HD Called<FF> dbl(const Called<FF>& a) {
     return Called<FF>{a.v + a.v};
 }
@@ -690,6 +694,20 @@ GG_HD Called<FF> operator*(const Called<FF>& a, const Called<FF>& b) {
 template <class FF>
 GG_HD Called<FF> sqr(const Called<FF>& a) {
     return Called<FF>{sqr_call(a.v)};
+}
+// a^(p - 2) in FpBls with the products as calls (p - 2 differs from p in the lowest limb only)
+inline GG_HDN FpBls inv_call(const FpBls& a) {
+    const Called<FpBls> b{a};
+    Called<FpBls> acc = Called<FpBls>::one();
+#pragma unroll
+    for (int w = FpBlsCfg::N - 1; w >= 0; w--) {
+        const uint32_t word = w == 0 ? FpBlsCfg::P[0] - 2u : FpBlsCfg::P[w];
+        for (int i = 31; i >= 0; i--) {
+            acc = sqr(acc);
+            if ((word >> i) & 1) acc = acc * b;
+        }
+    }
+    return acc.v;
 }
 template <class Tw, class FF>
 GG_HDN bool times_r_is_inf(const Affine<FF>& q) {

@@ -1,443 +1,72 @@
 // PlonK Verify for batches of BN254 proofs under one verifying key
 // (backend/plonk/bn254/verify.go:45-294), and the plain KZG opening check it
-// is made of (kzg.Verify).
-//
-// Every step is a per-lane GG_HD function; a kernel runs it over a grid and the
-// host path (gg_plonk_verify_batch_host) over a loop, on the same buffers.
-//
-//   pi_partial   lane (proof, slice of kPiSlice public inputs): sum L_i(zeta) x_i
-//                with one batch inversion (prefix products in a global workspace)
-//   fr_phase1    lane per proof: the point checks, zeta^n, L_1(zeta), PI(zeta), the
-//                quotient identity, the scalars of the two G1 combinations
-//   term_mul     lane (item, term): one scalar multiplication, an XYZZ partial
-//   group_sum    lane per item: the partials of its two groups -> two affine points
-//   pair2        lane per item: e(A, G2) e(B, [tau]G2) == 1, both Miller operands
-//                from the key's line tables
-//
-// Per batch: Fiat-Shamir and the BSB22 hashes on the host; pi_partial,
-// fr_phase1, term_mul, group_sum (foldedH and the linearised digest) on the
-// device; the KZG folding challenge and lambda on the host; term_mul, group_sum
-// (A and B), pair2 on the device.  DESIGN.md §4 "PlonK Verify".
-#include "common.h"
-#include "pairing.cuh"
-#include "pairing_host.h"
-#include "prof.h"
-#include "sha256.h"
-#include "transcript.h"
-#include <cstring>
-#include <mutex>
-#include <algorithm>
-#include <string>
-#include <thread>
-#include <vector>
+// is made of (kzg.Verify): plonk_verify_impl.cuh over Bn254Tower.  The steps,
+// the batch driver and the KZG driver are the header's; this file holds the
+// curve's traits, the five kernels and the C entry points.  The point checks are
+// the curve equation (cofactor 1), chained in fr_phase1; the point loops run
+// over Fp with the products inlined.  BLS12-381: plonk_verify_bls.hip.
+#include "plonk_verify_impl.cuh"
 
 namespace gg {
 namespace plonkv {
 
-using namespace gg::pairing;
-using Tw = Bn254Tower;
-using GT = Fp12<Tw>;
-using LineT = Line<Tw>;
-constexpr int kLines = line_count<Tw>();
-constexpr int kPiSlice = 32;  // public inputs per lane of pi_partial
-constexpr uint8_t kOk = GG_PLONK_VERIFY_OK;
-
-struct KeyConst {
-    uint64_t size = 0, nb_public = 0;
-    int log_n = 0;
-    uint32_t nc = 0;
-    Fr omega, omega_inv, u, size_fr;  // Montgomery
-};
-// the proof's byte layout (gnark_amd.h, gg_plonk_prove): 64-B points, 32-B fr
-struct Layout {
-    size_t nc = 0;
-    GG_HD size_t n_points() const { return 9 + nc; }
-    // LRO 0..2, Z 3, H 4..6, Bsb22 7..7+nc-1, BatchedProof.H 7+nc, ZShiftedOpening.H 8+nc
-    GG_HD size_t point(size_t k) const { return k < 8 + nc ? 64 * k : zs_h(); }
-    GG_HD size_t claimed(size_t j) const { return 64 * (8 + nc) + 32 * j; }
-    GG_HD size_t zs_h() const { return claimed(7 + nc); }
-    GG_HD size_t zu() const { return zs_h() + 64; }
-    GG_HD size_t stride() const { return zu() + 32; }
-};
-struct Chal {
-    Fr gamma, beta, alpha, zeta;
-};
-// where a term's point lives: 0 = the item's slot of buffer 0 (+ off), 1 = of buffer 1, 2 = the key's points
-struct TermSrc {
-    uint32_t kind, off;
-};
-
-template <class F>
-GG_HD const F& at(const uint8_t* base, size_t off) {
-    return *reinterpret_cast<const F*>(base + off);
-}
-
-// ---------------------------------------------------------------- per-lane steps
-struct PiArgs {
-    KeyConst k;
-    size_t n, nslices;
-    const Fr* wit;
-    const Chal* chal;
-    const uint8_t* status;
-    Fr* work;  // kPiSlice prefix products per lane
-    Fr* part;
-};
-GG_HD void pi_partial(const PiArgs& a, size_t id) {
-    const size_t p = id / a.nslices, s = id - p * a.nslices;
-    if (a.status[p] != kOk) return;
-    const Fr zeta = a.chal[p].zeta;
-    Fr zn = zeta;
-    for (int i = 0; i < a.k.log_n; i++) zn = sqr(zn);
-    const size_t i0 = s * kPiSlice, i1 = i0 + kPiSlice < a.k.nb_public ? i0 + kPiSlice : a.k.nb_public;
-    Fr* pre = a.work + id * kPiSlice;
-    // denominators n (zeta - w^i); a zero one stays out of the product and inverts to 0
-    Fr acc = Fr::one(), w = pow_u64(a.k.omega, i0);
-    for (size_t i = i0; i < i1; i++) {
-        pre[i - i0] = acc;
-        const Fr d = (zeta - w) * a.k.size_fr;
-        if (!d.is_zero()) acc = acc * d;
-        w = w * a.k.omega;
+struct Bn254 {
+    using Tw = Bn254Tower;
+    using Fr = gg::Fr;
+    using PC = Fp;
+    using P1Extra = NoFlags;
+    static constexpr int kCurve = GG_CURVE_BN254;
+    static constexpr bool kCheckLanes = false;
+    static GG_HD Fp inv(const Fp& a) { return inverse(a); }
+    static GG_HD int g1_flag(const G1Affine& p) { return g1_check<Tw>(p); }
+    static int g2_flag(const G2Affine& q) { return g2_check<Tw>(q); }
+    // G1Affine.RawBytes = Marshal of bn254: X | Y big-endian, the infinity all zeros
+    static void g1_raw(const G1Affine& p, uint8_t out[64]) {
+        fs::be_bytes<8>(from_mont(p.x).v, out);
+        fs::be_bytes<8>(from_mont(p.y).v, out + 32);
     }
-    Fr inv = inverse(acc), sum = Fr::zero();
-    for (size_t i = i1; i-- > i0;) {
-        w = w * a.k.omega_inv;
-        const Fr d = (zeta - w) * a.k.size_fr;
-        if (!d.is_zero()) {
-            sum = sum + w * (inv * pre[i - i0]) * a.wit[p * a.k.nb_public + i];
-            inv = inv * d;
-        }
+    static gg::Fr hash_to_field(const uint8_t* msg, size_t len, const uint8_t* dst, size_t dst_len) {
+        return pairing::hash_to_field(msg, len, dst, dst_len);
     }
-    a.part[id] = sum * (zn - Fr::one());
-}
-
-GG_HD void store_canonical(uint32_t* out, const Fr& mont) {
-    const Fr c = from_mont(mont);
-#pragma unroll
-    for (int i = 0; i < 8; i++) out[i] = c.v[i];
-}
-
-struct P1Args {
-    KeyConst k;
-    Layout L;
-    size_t n, nslices;
-    const uint8_t* proofs;
-    const Chal* chal;
-    const Fr* hashes;  // n x nc
-    const Fr* cmt_w;   // w^(nb_public + commitment_indexes[j])
-    const Fr* part;
-    uint8_t* status;
-    uint32_t* scal;  // n x (10 + nc) canonical scalars
 };
-GG_HD void fr_phase1(const P1Args& a, size_t p) {
-    if (a.status[p] != kOk) return;
-    const uint8_t* pr = a.proofs + p * a.L.stride();
-    const size_t nc = a.k.nc;
-    bool bad = false;
-    for (size_t k = 0; k < a.L.n_points(); k++) bad = bad || g1_check<Tw>(at<G1Affine>(pr, a.L.point(k))) != 0;
-    if (bad) {
-        a.status[p] = GG_PLONK_VERIFY_MALFORMED;
-        return;
-    }
-    const Chal c = a.chal[p];
-    const Fr one = Fr::one();
-    Fr zn = c.zeta;
-    for (int i = 0; i < a.k.log_n; i++) zn = sqr(zn);
-    const Fr zn1 = zn - one;
-    const Fr lag1 = zn1 * inverse((c.zeta - one) * a.k.size_fr);
-    Fr pi = Fr::zero();
-    for (size_t s = 0; s < a.nslices; s++) pi = pi + a.part[p * a.nslices + s];
-    for (size_t j = 0; j < nc; j++) {
-        const Fr w = a.cmt_w[j];
-        pi = pi + w * zn1 * inverse((c.zeta - w) * a.k.size_fr) * a.hashes[p * nc + j];
-    }
-    const Fr hq = at<Fr>(pr, a.L.claimed(0)), lin = at<Fr>(pr, a.L.claimed(1)), l = at<Fr>(pr, a.L.claimed(2)),
-             r = at<Fr>(pr, a.L.claimed(3)), o = at<Fr>(pr, a.L.claimed(4)), s1 = at<Fr>(pr, a.L.claimed(5)),
-             s2 = at<Fr>(pr, a.L.claimed(6)), zu = at<Fr>(pr, a.L.zu());
-    const Fr v1 = s1 * c.beta + l + c.gamma, v2 = s2 * c.beta + r + c.gamma;
-    const Fr a2l = lag1 * c.alpha * c.alpha;  // alpha^2 L_1(zeta)
-    const Fr t = v1 * v2 * (o + c.gamma) * c.alpha * zu;
-    if (hq != (lin + pi + t - a2l) * inverse(zn1)) {
-        a.status[p] = GG_PLONK_VERIFY_QUOTIENT;
-        return;
-    }
-    const Fr zp = zn * sqr(c.zeta);  // zeta^(n + 2)
-    const Fr bz = c.beta * c.zeta;
-    const Fr a1 = zu * c.beta * v1 * v2 * c.alpha;
-    const Fr a2 = a2l - (bz + l + c.gamma) * (bz * a.k.u + r + c.gamma) * (bz * sqr(a.k.u) + o + c.gamma) * c.alpha;
-    uint32_t* sc = a.scal + p * (10 + nc) * 8;
-    store_canonical(sc, one);  // H0, H1, H2
-    store_canonical(sc + 8, zp);
-    store_canonical(sc + 16, sqr(zp));
-    sc += 24;
-    for (size_t j = 0; j < nc; j++) store_canonical(sc + 8 * j, at<Fr>(pr, a.L.claimed(7 + j)));  // Bsb22_j
-    sc += 8 * nc;
-    store_canonical(sc, l);  // Ql Qr Qm Qo Qk S3 Z
-    store_canonical(sc + 8, r);
-    store_canonical(sc + 16, l * r);
-    store_canonical(sc + 24, o);
-    store_canonical(sc + 32, one);
-    store_canonical(sc + 40, a1);
-    store_canonical(sc + 48, a2);
-}
+using V = Verifier<Bn254>;
 
-// k a, k canonical in memory (8 words): double-and-add from the top bit with
-// mixed additions; the doubling is skipped while the accumulator is infinity.
-// Exact for k = 0, 1, k >= 2^253 and a = infinity.
-GG_HDN G1Xyzz g1_mul(const G1Affine& a, const uint32_t* k) {
-    G1Xyzz acc = G1Xyzz::inf();
-    if (a.is_inf()) return acc;
-    for (int wd = 7; wd >= 0; wd--) {
-        const uint32_t word = k[wd];
-        for (int b = 31; b >= 0; b--) {
-            if (!acc.is_inf()) acc = xyzz_dbl(acc);
-            if ((word >> b) & 1) xyzz_madd_inplace(acc, a);
-        }
-    }
-    return acc;
-}
-
-struct MulArgs {
-    size_t n, T;
-    const TermSrc* src;
-    const uint8_t *b0, *b1, *key;
-    size_t s0, s1;  // bytes per item of b0, b1
-    const uint32_t* scal;
-    const uint8_t* status;
-    G1Xyzz* part;
-};
-GG_HD void term_mul(const MulArgs& a, size_t id) {
-    const size_t p = id / a.T, t = id - p * a.T;
-    if (a.status[p] != kOk) return;
-    const TermSrc s = a.src[t];
-    const uint8_t* base = s.kind == 0 ? a.b0 + p * a.s0 : s.kind == 1 ? a.b1 + p * a.s1 : a.key;
-    a.part[id] = g1_mul(at<G1Affine>(base, s.off), a.scal + id * 8);
-}
-
-GG_HD G1Affine xyzz_to_affine(const G1Xyzz& p) {
-    if (p.is_inf()) return G1Affine::inf();
-    const Fp i3 = inverse(p.zzz);
-    return G1Affine{p.x * sqr(p.zz * i3), p.y * i3};
-}
-struct SumArgs {
-    size_t n, T, split;
-    bool neg;  // negate the second group's sum
-    const uint8_t* status;
-    const G1Xyzz* part;
-    G1Affine* out;  // [2 p]: sum of terms [0, split), [2 p + 1]: of [split, T)
-};
-GG_HD void group_sum(const SumArgs& a, size_t p) {
-    if (a.status[p] != kOk) return;
-    G1Xyzz acc = G1Xyzz::inf();
-    for (size_t t = 0; t < a.split; t++) xyzz_add_inplace(acc, a.part[p * a.T + t]);
-    a.out[2 * p] = xyzz_to_affine(acc);
-    acc = G1Xyzz::inf();
-    for (size_t t = a.split; t < a.T; t++) xyzz_add_inplace(acc, a.part[p * a.T + t]);
-    const G1Affine b = xyzz_to_affine(acc);
-    a.out[2 * p + 1] = a.neg ? neg(b) : b;
-}
-
-struct PairArgs {
-    size_t n;
-    const G1Affine* pts;  // A, B per item
-    const LineT *t0, *t1;  // the lines of G2 and of [tau]G2
-    uint8_t* status;
-    uint8_t fail;
-};
-GG_HD void pair2(const PairArgs& a, size_t i) {
-    if (a.status[i] != kOk) return;
-    G1Affine p[2];
-    G2Src<Tw> s[2];
-    p[0] = a.pts[2 * i];
-    p[1] = a.pts[2 * i + 1];
-    s[0].tab = a.t0;
-    s[0].skip = p[0].is_inf();
-    s[1].tab = a.t1;
-    s[1].skip = p[1].is_inf();
-    GT f = GT::one();
-    miller_loop<Tw, 2>(f, p, s);
-    if (!final_exp(f).is_one()) a.status[i] = a.fail;
-}
-
-__global__ void __launch_bounds__(256) k_pv_pi(PiArgs a) {
+__global__ void __launch_bounds__(256) k_pv_pi(V::PiArgs a) {
     const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id < a.n * a.nslices) pi_partial(a, id);
+    if (id < a.n * a.nslices) V::pi_partial(a, id);
 }
-__global__ void __launch_bounds__(256) k_pv_fr(P1Args a) {
+__global__ void __launch_bounds__(256) k_pv_fr(V::P1Args a) {
     const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id < a.n) fr_phase1(a, id);
+    if (id < a.n) V::fr_phase1(a, id);
 }
-__global__ void __launch_bounds__(64) k_pv_mul(MulArgs a) {
+__global__ void __launch_bounds__(64) k_pv_mul(V::MulArgs a) {
     const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id < a.n * a.T) term_mul(a, id);
+    if (id < a.n * a.T) V::term_mul(a, id);
 }
-__global__ void __launch_bounds__(64) k_pv_sum(SumArgs a) {
+__global__ void __launch_bounds__(64) k_pv_sum(V::SumArgs a) {
     const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id < a.n) group_sum(a, id);
+    if (id < a.n) V::group_sum(a, id);
 }
-__global__ void __launch_bounds__(64) k_pv_pair(PairArgs a) {
+__global__ void __launch_bounds__(64) k_pv_pair(V::PairArgs a) {
     const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id < a.n) pair2(a, id);
+    if (id < a.n) V::pair2(a, id);
 }
-
-// ---------------------------------------------------------------- host side
-// One step over `count` lanes: a kernel launch on st, or a loop on this thread.
-template <class A>
-static void run(bool dev, hipStream_t st, void (*kern)(A), void (*body)(const A&, size_t), const A& a, size_t count,
-                unsigned block) {
-    if (!count) return;
-    if (dev) {
-        hipLaunchKernelGGL(kern, dim3(grid_for(count, block)), dim3(block), 0, st, a);
-        GG_HIP(hipGetLastError());
-    } else {
-        for (size_t i = 0; i < count; i++) body(a, i);
-    }
-}
-// a grow-only buffer on either side
-struct Buf {
-    DevBuf d;
-    std::vector<uint8_t> h;
-    void* get(bool dev, size_t bytes) {
-        if (dev) {
-            d.reserve(bytes > 16 ? bytes : 16);
-            return d.p;
-        }
-        if (h.size() < bytes + 16) h.resize(bytes + 16);
-        return h.data();
-    }
-    // the step's view of host data: the data itself, or an upload on st
-    const void* in(bool dev, const void* host, size_t bytes, hipStream_t st) {
-        if (!dev) return host;
-        void* p = get(true, bytes);
-        if (bytes) GG_HIP(hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, st));
-        return p;
-    }
+template <>
+struct Kernels<Bn254> {
+    static constexpr auto pi = k_pv_pi;
+    static constexpr auto fr = k_pv_fr;
+    static constexpr auto mul = k_pv_mul;
+    static constexpr auto sum = k_pv_sum;
+    static constexpr auto pair = k_pv_pair;
 };
-static void fetch(bool dev, void* host, const void* src, size_t bytes, hipStream_t st) {
-    if (dev) {
-        GG_HIP(hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, st));
-        GG_WAIT_STREAM(st);
-    } else if (host != src) {
-        memcpy(host, src, bytes);
-    }
-}
-struct Work {
-    Buf proofs, wit, chal, hashes, status, piwork, pipart, scal, part, pts, extra;
-};
-
-template <class F>
-static bool is_canonical(const F& x) {
-    const F m = F::modulus();
-    for (int i = 7; i >= 0; i--)
-        if (x.v[i] != m.v[i]) return x.v[i] < m.v[i];
-    return false;
-}
-static void fr_be(const Fr& mont, uint8_t out[32]) { fs::be_bytes<8>(from_mont(mont).v, out); }
-// G1Affine.RawBytes = Marshal of bn254: X | Y big-endian, the infinity all zeros
-static void g1_raw(const G1Affine& p, uint8_t out[64]) {
-    fs::be_bytes<8>(from_mont(p.x).v, out);
-    fs::be_bytes<8>(from_mont(p.y).v, out + 32);
-}
-static bool g1_canonical(const G1Affine& p) { return is_canonical(p.x) && is_canonical(p.y); }
-static void put_canonical(std::vector<uint32_t>& v, size_t slot, const Fr& mont) {
-    const Fr c = from_mont(mont);
-    memcpy(&v[8 * slot], c.v, 32);
-}
-static const uint8_t kBsb22Dst[] = "BSB22-Plonk";          // verify.go:128
-static const uint8_t kLambdaTag[] = "gg-plonk-kzg-lambda";  // the batch-opening coefficient's domain
-
-// kzg_g2 = {G2, [tau]G2}: checked, then their line tables (2 x kLines)
-static void g2_tables(const void* kzg_g2, std::vector<LineT>& lines) {
-    G2Affine q[2];
-    memcpy(q, kzg_g2, sizeof(q));
-    for (int t = 0; t < 2; t++) {
-        const std::string nm = "kzg_g2[" + std::to_string(t) + "]";
-        GG_CHECK(!q[t].is_inf(), GG_ERR_INVALID_ARG, nm + " is the point at infinity");
-        GG_CHECK(is_canonical(q[t].x.a0) && is_canonical(q[t].x.a1) && is_canonical(q[t].y.a0) &&
-                     is_canonical(q[t].y.a1),
-                 GG_ERR_INVALID_ARG, nm + " has a coordinate >= p");
-        const int f = g2_check<Tw>(q[t]);
-        GG_CHECK(f != 1, GG_ERR_INVALID_ARG, nm + " is not on the twist");
-        GG_CHECK(f == 0, GG_ERR_INVALID_ARG, nm + " is not in the r-torsion");
-    }
-    lines.resize((size_t)2 * kLines);
-    for (int t = 0; t < 2; t++) line_table<Tw>(q[t], lines.data() + (size_t)t * kLines);
-}
-static G1Affine checked_g1(const void* p, size_t i, const std::string& name) {
-    G1Affine a;
-    memcpy(&a, (const uint8_t*)p + 64 * i, 64);
-    GG_CHECK(g1_canonical(a) && g1_check<Tw>(a) == 0, GG_ERR_INVALID_ARG, name + " is not on the curve");
-    return a;
-}
-
-// The per-proof host work (transcripts, hashes) over [0, n): on kHostThreads
-// threads when the hashes are the library's SHA-256; a caller's hash callback
-// and its context are not assumed to be thread-safe, so they run on this thread.
-constexpr size_t kHostThreads = 8, kHostGrain = 64;
-template <class Fn>
-static void host_for(size_t n, bool parallel, Fn fn) {
-    const size_t nt = parallel ? std::min(kHostThreads, n / kHostGrain) : 0;
-    if (nt < 2) {
-        for (size_t i = 0; i < n; i++) fn(i);
-        return;
-    }
-    std::mutex emu;
-    int code = GG_OK;
-    std::string err;
-    auto worker = [&](size_t t) {
-        try {
-            for (size_t i = n * t / nt; i < n * (t + 1) / nt; i++) fn(i);
-        } catch (const Error& e) {
-            std::lock_guard<std::mutex> g(emu);
-            code = e.code;
-            err = e.what();
-        } catch (const std::exception& e) {
-            std::lock_guard<std::mutex> g(emu);
-            code = GG_ERR_INTERNAL;
-            err = e.what();
-        }
-    };
-    std::vector<std::thread> th;
-    for (size_t t = 1; t < nt; t++) th.emplace_back(worker, t);
-    worker(0);
-    for (auto& x : th) x.join();
-    GG_CHECK(code == GG_OK, code, err);
-}
-
-// terms -> partials -> the two group sums of every item, in w.pts (2 affine per item)
-static G1Affine* combine(bool dev, hipStream_t st, Work& w, size_t n, size_t T, size_t split, bool neg,
-                         const TermSrc* src, const uint8_t* b0, size_t s0, const uint8_t* b1, size_t s1,
-                         const uint8_t* key, const uint32_t* scal, const uint8_t* status) {
-    MulArgs m{n, T, src, b0, b1, key, s0, s1, scal, status, (G1Xyzz*)w.part.get(dev, n * T * sizeof(G1Xyzz))};
-    run(dev, st, k_pv_mul, term_mul, m, n * T, 64);
-    SumArgs s{n, T, split, neg, status, m.part, (G1Affine*)w.pts.get(dev, 2 * n * sizeof(G1Affine))};
-    run(dev, st, k_pv_sum, group_sum, s, n, 64);
-    return s.out;
-}
 
 }  // namespace plonkv
 }  // namespace gg
 
 using namespace gg;
-using namespace gg::plonkv;
+using V = gg::plonkv::V;
 
-struct gg_plonk_vk {
-    KeyConst k;
-    Layout L;
-    std::vector<Fr> cmt_w;
-    std::vector<G1Affine> pts;  // S1 S2 S3 Ql Qr Qm Qo Qk Qcp[nc] G
-    std::vector<LineT> lines;   // G2, [tau]G2: kLines each
-    std::vector<uint8_t> bound;  // the key's part of the gamma bindings (bindPublicData)
-    std::vector<TermSrc> src1, src2;
-    std::mutex mu;  // one batch at a time per key: the buffers below are the key's
-    bool uploaded = false;
-    int device = 0;
-    hipStream_t st = nullptr;
-    DevBuf d_pts, d_lines, d_cmt_w, d_src1, d_src2;
-    Work dev, host;
-    ~gg_plonk_vk() {
-        if (st) (void)hipStreamDestroy(st);
-    }
-};
+struct gg_plonk_vk : V::Key {};
 
 extern "C" int gg_plonk_vk_create(int curve, uint64_t size, const void* generator, const void* coset_shift,
                                   const void* S, const void* Q, const void* Qcp, int n_cmt,
@@ -447,82 +76,11 @@ extern "C" int gg_plonk_vk_create(int curve, uint64_t size, const void* generato
     GG_CHECK(out, GG_ERR_INVALID_ARG, "null argument: out");
     *out = nullptr;
     GG_CHECK(curve == GG_CURVE_BN254, GG_ERR_UNSUPPORTED,
-             "curve " + std::to_string(curve) + " is not supported: PlonK Verify has a BN254 pairing only");
-    GG_CHECK(generator, GG_ERR_INVALID_ARG, "null argument: generator");
-    GG_CHECK(coset_shift, GG_ERR_INVALID_ARG, "null argument: coset_shift");
-    GG_CHECK(S, GG_ERR_INVALID_ARG, "null argument: S");
-    GG_CHECK(Q, GG_ERR_INVALID_ARG, "null argument: Q");
-    GG_CHECK(kzg_g1, GG_ERR_INVALID_ARG, "null argument: kzg_g1");
-    GG_CHECK(kzg_g2, GG_ERR_INVALID_ARG, "null argument: kzg_g2");
-    GG_CHECK(n_cmt >= 0, GG_ERR_INVALID_ARG, "n_cmt must be >= 0");
-    const size_t nc = (size_t)n_cmt;
-    GG_CHECK(Qcp || !nc, GG_ERR_INVALID_ARG, "null argument: Qcp");
-    GG_CHECK(commitment_indexes || !nc, GG_ERR_INVALID_ARG, "null argument: commitment_indexes");
-    GG_CHECK(size >= 2 && !(size & (size - 1)), GG_ERR_INVALID_ARG,
-             "size = " + std::to_string(size) + " must be a power of two >= 2");
-    GG_CHECK(nb_public <= size, GG_ERR_INVALID_ARG,
-             "nb_public = " + std::to_string(nb_public) + " exceeds size = " + std::to_string(size));
-    for (size_t j = 0; j < nc; j++)
-        GG_CHECK(nb_public + commitment_indexes[j] < size, GG_ERR_INVALID_ARG,
-                 "commitment index " + std::to_string(commitment_indexes[j]) + " of commitment " + std::to_string(j) +
-                     ": nb_public + index >= size = " + std::to_string(size));
+             "curve " + std::to_string(curve) +
+                 " is not supported: this entry point is BN254's (BLS12-381: gg_plonk_vk_create_bls12_381)");
     std::unique_ptr<gg_plonk_vk> vk(new gg_plonk_vk);
-    KeyConst& k = vk->k;
-    k.size = size;
-    k.nb_public = nb_public;
-    k.nc = (uint32_t)nc;
-    while (((uint64_t)1 << k.log_n) < size) k.log_n++;
-    memcpy(&k.omega, generator, 32);
-    memcpy(&k.u, coset_shift, 32);
-    GG_CHECK(is_canonical(k.omega) && !k.omega.is_zero(), GG_ERR_INVALID_ARG, "generator is zero or >= r");
-    GG_CHECK(is_canonical(k.u), GG_ERR_INVALID_ARG, "coset_shift is >= r");
-    k.omega_inv = inverse(k.omega);
-    k.size_fr = Fr::zero();
-    k.size_fr.v[0] = (uint32_t)size;
-    k.size_fr.v[1] = (uint32_t)(size >> 32);
-    k.size_fr = to_mont(k.size_fr);
-    vk->L.nc = nc;
-    GG_CHECK(gg_plonk_proof_size_ex(curve, n_cmt) == vk->L.stride(), GG_ERR_INTERNAL, "proof layout mismatch");
-    static const char* qn[5] = {"Ql", "Qr", "Qm", "Qo", "Qk"};
-    for (size_t i = 0; i < 3; i++) vk->pts.push_back(checked_g1(S, i, "S[" + std::to_string(i) + "]"));
-    for (size_t i = 0; i < 5; i++) vk->pts.push_back(checked_g1(Q, i, qn[i]));
-    for (size_t i = 0; i < nc; i++) vk->pts.push_back(checked_g1(Qcp, i, "Qcp[" + std::to_string(i) + "]"));
-    vk->pts.push_back(checked_g1(kzg_g1, 0, "kzg_g1"));
-    g2_tables(kzg_g2, vk->lines);
-    for (size_t j = 0; j < nc; j++) {
-        Fr w = Fr::one(), b = k.omega;  // w^(nb_public + index) by square-and-multiply
-        for (uint64_t e = nb_public + commitment_indexes[j]; e; e >>= 1) {
-            if (e & 1) w = w * b;
-            b = sqr(b);
-        }
-        vk->cmt_w.push_back(w);
-    }
-    vk->bound.resize(64 * (8 + nc));
-    for (size_t i = 0; i < 8 + nc; i++) g1_raw(vk->pts[i], vk->bound.data() + 64 * i);
-    // the terms of the two combinations (points: key index i at 64 i)
-    const Layout& L = vk->L;
-    auto proof = [&](size_t point) { return TermSrc{0, (uint32_t)L.point(point)}; };
-    auto key = [](size_t i) { return TermSrc{2, (uint32_t)(64 * i)}; };
-    const size_t iG = 8 + nc;
-    std::vector<TermSrc>& s1 = vk->src1;  // H0 H1 H2 | Bsb22_j Ql Qr Qm Qo Qk S3 Z
-    for (size_t i = 0; i < 3; i++) s1.push_back(proof(4 + i));
-    for (size_t j = 0; j < nc; j++) s1.push_back(proof(7 + j));
-    for (size_t i = 0; i < 5; i++) s1.push_back(key(3 + i));
-    s1.push_back(key(2));
-    s1.push_back(proof(3));
-    std::vector<TermSrc>& s2 = vk->src2;  // foldedH lin L R O S1 S2 Qcp_j Z G H_b H_z | H_b H_z
-    s2.push_back(TermSrc{1, 0});
-    s2.push_back(TermSrc{1, 64});
-    for (size_t i = 0; i < 3; i++) s2.push_back(proof(i));
-    s2.push_back(key(0));
-    s2.push_back(key(1));
-    for (size_t j = 0; j < nc; j++) s2.push_back(key(8 + j));
-    s2.push_back(proof(3));
-    s2.push_back(key(iG));
-    s2.push_back(proof(7 + nc));
-    s2.push_back(proof(8 + nc));
-    s2.push_back(proof(7 + nc));
-    s2.push_back(proof(8 + nc));
+    V::create_key(vk.get(), size, generator, coset_shift, S, Q, Qcp, n_cmt, commitment_indexes, nb_public, kzg_g1,
+                  kzg_g2);
     *out = vk.release();
     GG_CAPI_END
 }
@@ -532,275 +90,33 @@ extern "C" int gg_plonk_vk_destroy(gg_plonk_vk_t vk) {
     GG_CAPI_END
 }
 
-static void verify_batch(gg_plonk_vk* vk, bool dev, size_t n, const void* proofs, const void* public_witness,
-                         gg_hash_fn challenge_hash, void* challenge_ctx, gg_hash_fn folding_hash, void* folding_ctx,
-                         uint8_t* status_out) {
-    GG_CHECK(vk, GG_ERR_INVALID_ARG, "null argument: vk");
-    GG_CHECK(n > 0, GG_ERR_INVALID_ARG, "n must be > 0");
-    GG_CHECK(n <= ((size_t)1 << 24), GG_ERR_INVALID_ARG, "n exceeds 2^24 proofs per call");
-    GG_CHECK(proofs, GG_ERR_INVALID_ARG, "null argument: proofs");
-    GG_CHECK(status_out, GG_ERR_INVALID_ARG, "null argument: status_out");
-    const KeyConst& k = vk->k;
-    const Layout& L = vk->L;
-    const size_t nc = k.nc, nw = k.nb_public, stride = L.stride();
-    GG_CHECK(public_witness || !nw, GG_ERR_INVALID_ARG, "null argument: public_witness");
-    std::lock_guard<std::mutex> lock(vk->mu);
-    hipStream_t st = nullptr;
-    const uint8_t *key_pts = (const uint8_t*)vk->pts.data();
-    const LineT* lines = vk->lines.data();
-    const Fr* cmt_w = vk->cmt_w.data();
-    const TermSrc *src1 = vk->src1.data(), *src2 = vk->src2.data();
-    if (dev) {
-        if (!vk->uploaded) {  // the first device batch: the key and its tables
-            GG_HIP(hipGetDevice(&vk->device));
-            if (!vk->st) GG_HIP(hipStreamCreateWithFlags(&vk->st, hipStreamNonBlocking));
-            upload(vk->d_pts, vk->pts.data(), vk->pts.size() * sizeof(G1Affine), vk->st);
-            upload(vk->d_lines, vk->lines.data(), vk->lines.size() * sizeof(LineT), vk->st);
-            upload(vk->d_cmt_w, vk->cmt_w.data(), vk->cmt_w.size() * sizeof(Fr), vk->st);
-            upload(vk->d_src1, vk->src1.data(), vk->src1.size() * sizeof(TermSrc), vk->st);
-            upload(vk->d_src2, vk->src2.data(), vk->src2.size() * sizeof(TermSrc), vk->st);
-            GG_WAIT_STREAM(vk->st);
-            vk->uploaded = true;
-        }
-        GG_HIP(hipSetDevice(vk->device));
-        st = vk->st;
-        key_pts = (const uint8_t*)vk->d_pts.p;
-        lines = vk->d_lines.as<LineT>();
-        cmt_w = vk->d_cmt_w.as<Fr>();
-        src1 = vk->d_src1.as<TermSrc>();
-        src2 = vk->d_src2.as<TermSrc>();
-    }
-    Work& w = dev ? vk->dev : vk->host;
-    const uint8_t* P = (const uint8_t*)proofs;
-    const Fr* W = (const Fr*)public_witness;
-    const fs::Hasher ch{challenge_hash, challenge_ctx}, fh{folding_hash, folding_ctx};
-
-    // ---- host: canonical values, gamma beta alpha zeta, the BSB22 hashes
-    std::vector<uint8_t> status(n, kOk);
-    std::vector<Chal> chal(n);
-    std::vector<Fr> hashes(n * nc);
-    const bool par = !challenge_hash && !folding_hash;
-    host_for(n, par, [&](size_t i) {
-        uint8_t b32[32], b64[64];
-        const uint8_t* pr = P + i * stride;
-        bool ok = is_canonical(at<Fr>(pr, L.zu()));
-        for (size_t j = 0; j < 7 + nc; j++) ok = ok && is_canonical(at<Fr>(pr, L.claimed(j)));
-        for (size_t j = 0; j < nw; j++) ok = ok && is_canonical(W[i * nw + j]);
-        for (size_t j = 0; j < L.n_points(); j++) ok = ok && g1_canonical(at<G1Affine>(pr, L.point(j)));
-        if (!ok) {
-            status[i] = GG_PLONK_VERIFY_MALFORMED;
-            return;
-        }
-        fs::Transcript<Fr> t({"gamma", "beta", "alpha", "zeta"}, ch);
-        t.bind("gamma", vk->bound.data(), vk->bound.size());
-        for (size_t j = 0; j < nw; j++) {
-            fr_be(W[i * nw + j], b32);
-            t.bind("gamma", b32, 32);
-        }
-        auto bind_pt = [&](const char* name, size_t point) {
-            g1_raw(at<G1Affine>(pr, L.point(point)), b64);
-            t.bind(name, b64, 64);
-        };
-        for (size_t j = 0; j < 3; j++) bind_pt("gamma", j);
-        chal[i].gamma = t.compute("gamma");
-        chal[i].beta = t.compute("beta");
-        for (size_t j = 0; j < nc; j++) bind_pt("alpha", 7 + j);
-        bind_pt("alpha", 3);
-        chal[i].alpha = t.compute("alpha");
-        for (size_t j = 0; j < 3; j++) bind_pt("zeta", 4 + j);
-        chal[i].zeta = t.compute("zeta");
-        for (size_t j = 0; j < nc; j++) {
-            g1_raw(at<G1Affine>(pr, L.point(7 + j)), b64);
-            hashes[i * nc + j] = hash_to_field(b64, 64, kBsb22Dst, sizeof(kBsb22Dst) - 1);
-        }
-    });
-
-    // ---- phase 1: PI(zeta), the quotient identity, foldedH and the linearised digest
-    const size_t nslices = (nw + kPiSlice - 1) / kPiSlice, T1 = 10 + nc, T2 = 13 + nc;
-    const uint8_t* dP = (const uint8_t*)w.proofs.in(dev, P, n * stride, st);
-    const Fr* dW = (const Fr*)w.wit.in(dev, W, n * nw * sizeof(Fr), st);
-    const Chal* dC = (const Chal*)w.chal.in(dev, chal.data(), n * sizeof(Chal), st);
-    const Fr* dH = (const Fr*)w.hashes.in(dev, hashes.data(), hashes.size() * sizeof(Fr), st);
-    uint8_t* dS = (uint8_t*)w.status.get(dev, n);
-    if (dev) GG_HIP(hipMemcpyAsync(dS, status.data(), n, hipMemcpyHostToDevice, st));
-    else memcpy(dS, status.data(), n);
-    std::vector<G1Affine> fl(2 * n);  // foldedH, linearised digest
-    {
-        ProfScope prof("plonk_verify_phase1", st, (double)n);
-        PiArgs pa{k, n, nslices, dW, dC, dS, (Fr*)w.piwork.get(dev, n * nslices * kPiSlice * sizeof(Fr)),
-                  (Fr*)w.pipart.get(dev, n * nslices * sizeof(Fr))};
-        run(dev, st, k_pv_pi, pi_partial, pa, n * nslices, 256);
-        P1Args p1{k, L, n, nslices, dP, dC, dH, cmt_w, pa.part, dS, (uint32_t*)w.scal.get(dev, n * T2 * 32)};
-        run(dev, st, k_pv_fr, fr_phase1, p1, n, 256);
-        const G1Affine* o = combine(dev, st, w, n, T1, 3, false, src1, dP, stride, nullptr, 0, key_pts, p1.scal, dS);
-        if (dev) GG_HIP(hipMemcpyAsync(fl.data(), o, 2 * n * sizeof(G1Affine), hipMemcpyDeviceToHost, st));
-        else memcpy(fl.data(), o, 2 * n * sizeof(G1Affine));
-        fetch(dev, status.data(), dS, n, st);
-        prof.stop(st);
-    }
-
-    // ---- host: the KZG folding challenge, lambda, the scalars of A and B
-    std::vector<uint32_t> scal(n * T2 * 8, 0);
-    host_for(n, par, [&](size_t i) {
-        if (status[i] != kOk) return;
-        uint8_t b32[32], b64[64];
-        const uint8_t* pr = P + i * stride;
-        const Fr zeta = chal[i].zeta, zu = at<Fr>(pr, L.zu());
-        fs::Transcript<Fr> t({"gamma"}, fh);
-        fr_be(zeta, b32);
-        t.bind("gamma", b32, 32);
-        auto bind_g1 = [&](const G1Affine& p) {
-            g1_raw(p, b64);
-            t.bind("gamma", b64, 64);
-        };
-        bind_g1(fl[2 * i]);
-        bind_g1(fl[2 * i + 1]);
-        for (size_t j = 0; j < 3; j++) bind_g1(at<G1Affine>(pr, L.point(j)));
-        bind_g1(vk->pts[0]);
-        bind_g1(vk->pts[1]);
-        for (size_t j = 0; j < nc; j++) bind_g1(vk->pts[8 + j]);
-        for (size_t j = 0; j < 7 + nc; j++) {
-            fr_be(at<Fr>(pr, L.claimed(j)), b32);
-            t.bind("gamma", b32, 32);
-        }
-        fr_be(zu, b32);
-        t.bind("gamma", b32, 32);
-        const Fr gk = t.compute("gamma");
-        // lambda = SHA-256(tag | gk | RawBytes(BatchedProof.H) | RawBytes(ZShiftedOpening.H)) mod r, 0 -> 1
-        Sha256 sh;
-        sh.update(kLambdaTag, sizeof(kLambdaTag) - 1);
-        fr_be(gk, b32);
-        sh.update(b32, 32);
-        g1_raw(at<G1Affine>(pr, L.point(7 + nc)), b64);
-        sh.update(b64, 64);
-        g1_raw(at<G1Affine>(pr, L.point(8 + nc)), b64);
-        sh.update(b64, 64);
-        sh.final(b32);
-        Fr lambda = fs::fr_set_bytes<Fr>(b32, 32);
-        if (lambda.is_zero()) lambda = Fr::one();
-        // A: gk^j D_j (7 + nc digests), lambda Z, -(sum gk^j y_j + lambda zu) G, zeta H_b, lambda zeta w H_z
-        // B: H_b, lambda H_z (negated by the sum)
-        const size_t s0 = i * T2;
-        Fr g = Fr::one(), fy = Fr::zero();
-        for (size_t j = 0; j < 7 + nc; j++) {
-            put_canonical(scal, s0 + j, g);
-            fy = fy + g * at<Fr>(pr, L.claimed(j));
-            g = g * gk;
-        }
-        put_canonical(scal, s0 + 7 + nc, lambda);
-        put_canonical(scal, s0 + 8 + nc, -(fy + lambda * zu));
-        put_canonical(scal, s0 + 9 + nc, zeta);
-        put_canonical(scal, s0 + 10 + nc, lambda * zeta * k.omega);
-        put_canonical(scal, s0 + 11 + nc, Fr::one());
-        put_canonical(scal, s0 + 12 + nc, lambda);
-    });
-
-    // ---- phase 2: A, B and e(A, G2) e(B, [tau]G2) == 1
-    {
-        ProfScope prof("plonk_verify_phase2", st, (double)n);
-        const uint8_t* dE = (const uint8_t*)w.extra.in(dev, fl.data(), 2 * n * sizeof(G1Affine), st);
-        const uint32_t* dSc = (const uint32_t*)w.scal.in(dev, scal.data(), scal.size() * 4, st);
-        const G1Affine* ab = combine(dev, st, w, n, T2, 11 + nc, true, src2, dP, stride, dE, 2 * sizeof(G1Affine),
-                                     key_pts, dSc, dS);
-        PairArgs pa{n, ab, lines, lines + kLines, dS, GG_PLONK_VERIFY_KZG};
-        run(dev, st, k_pv_pair, pair2, pa, n, 64);
-        fetch(dev, status_out, dS, n, st);
-        prof.stop(st);
-    }
-}
-
 extern "C" int gg_plonk_verify_batch(gg_plonk_vk_t vk, size_t n, const void* proofs, const void* public_witness,
                                      gg_hash_fn challenge_hash, void* challenge_ctx, gg_hash_fn folding_hash,
                                      void* folding_ctx, uint8_t* status_out) {
     GG_CAPI_BEGIN
-    verify_batch(vk, true, n, proofs, public_witness, challenge_hash, challenge_ctx, folding_hash, folding_ctx,
-                 status_out);
+    V::verify_batch(vk, true, n, proofs, public_witness, challenge_hash, challenge_ctx, folding_hash, folding_ctx,
+                    status_out);
     GG_CAPI_END
 }
 extern "C" int gg_plonk_verify_batch_host(gg_plonk_vk_t vk, size_t n, const void* proofs, const void* public_witness,
                                           gg_hash_fn challenge_hash, void* challenge_ctx, gg_hash_fn folding_hash,
                                           void* folding_ctx, uint8_t* status_out) {
     GG_CAPI_BEGIN
-    verify_batch(vk, false, n, proofs, public_witness, challenge_hash, challenge_ctx, folding_hash, folding_ctx,
-                 status_out);
+    V::verify_batch(vk, false, n, proofs, public_witness, challenge_hash, challenge_ctx, folding_hash, folding_ctx,
+                    status_out);
     GG_CAPI_END
 }
 
-// kzg.Verify of n openings: A_i = C_i - y_i G + z_i H_i, B_i = -H_i, through
-// the PlonK path's term_mul / group_sum / pair2
-static void kzg_verify(bool dev, size_t n, const void* kzg_g1, const void* kzg_g2, const void* digests,
-                       const void* quotients, const void* points, const void* values, uint8_t* ok_out) {
-    GG_CHECK(n > 0, GG_ERR_INVALID_ARG, "n must be > 0");
-    GG_CHECK(n <= ((size_t)1 << 24), GG_ERR_INVALID_ARG, "n exceeds 2^24 openings per call");
-    GG_CHECK(kzg_g1, GG_ERR_INVALID_ARG, "null argument: kzg_g1");
-    GG_CHECK(kzg_g2, GG_ERR_INVALID_ARG, "null argument: kzg_g2");
-    GG_CHECK(digests, GG_ERR_INVALID_ARG, "null argument: digests");
-    GG_CHECK(quotients, GG_ERR_INVALID_ARG, "null argument: quotients");
-    GG_CHECK(points, GG_ERR_INVALID_ARG, "null argument: points");
-    GG_CHECK(values, GG_ERR_INVALID_ARG, "null argument: values");
-    GG_CHECK(ok_out, GG_ERR_INVALID_ARG, "null argument: ok_out");
-    const G1Affine g = checked_g1(kzg_g1, 0, "kzg_g1");
-    std::vector<LineT> lines;
-    g2_tables(kzg_g2, lines);
-    const G1Affine *C = (const G1Affine*)digests, *H = (const G1Affine*)quotients;
-    const Fr *Z = (const Fr*)points, *Y = (const Fr*)values;
-    // C x 1, G x -y, H x z | H x 1; an off-curve point or a scalar >= r: rejected before any arithmetic
-    const TermSrc src[4] = {{0, 0}, {2, 0}, {1, 0}, {1, 0}};
-    std::vector<uint8_t> status(n, 0);
-    std::vector<uint32_t> scal(n * 4 * 8, 0);
-    for (size_t i = 0; i < n; i++) {
-        if (!(g1_canonical(C[i]) && g1_check<Tw>(C[i]) == 0 && g1_canonical(H[i]) && g1_check<Tw>(H[i]) == 0 &&
-              is_canonical(Z[i]) && is_canonical(Y[i]))) {
-            status[i] = 1;
-            continue;
-        }
-        put_canonical(scal, 4 * i, Fr::one());
-        put_canonical(scal, 4 * i + 1, -Y[i]);
-        put_canonical(scal, 4 * i + 2, Z[i]);
-        put_canonical(scal, 4 * i + 3, Fr::one());
-    }
-    Work w;
-    hipStream_t st = nullptr;
-    struct StreamGuard {
-        hipStream_t s = nullptr;
-        ~StreamGuard() {
-            if (s) (void)hipStreamDestroy(s);
-        }
-    } sg;
-    DevBuf d_lines, d_g, d_src;
-    const LineT* L = lines.data();
-    const uint8_t* key = (const uint8_t*)&g;
-    const TermSrc* dsrc = src;
-    if (dev) {
-        GG_HIP(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
-        st = sg.s;
-        upload(d_lines, lines.data(), lines.size() * sizeof(LineT), st);
-        upload(d_g, &g, sizeof(g), st);
-        upload(d_src, src, sizeof(src), st);
-        L = d_lines.as<LineT>();
-        key = (const uint8_t*)d_g.p;
-        dsrc = d_src.as<TermSrc>();
-    }
-    const uint8_t* dC = (const uint8_t*)w.proofs.in(dev, C, n * 64, st);
-    const uint8_t* dH = (const uint8_t*)w.extra.in(dev, H, n * 64, st);
-    const uint32_t* dSc = (const uint32_t*)w.scal.in(dev, scal.data(), scal.size() * 4, st);
-    uint8_t* dS = (uint8_t*)const_cast<void*>(w.status.in(dev, status.data(), n, st));
-    const G1Affine* ab = combine(dev, st, w, n, 4, 3, true, dsrc, dC, 64, dH, 64, key, dSc, dS);
-    PairArgs pa{n, ab, L, L + kLines, dS, 1};
-    run(dev, st, k_pv_pair, pair2, pa, n, 64);
-    fetch(dev, status.data(), dS, n, st);
-    for (size_t i = 0; i < n; i++) ok_out[i] = status[i] == 0 ? 1 : 0;
-}
 extern "C" int gg_kzg_verify_bn254(size_t n, const void* kzg_g1, const void* kzg_g2, const void* digests,
                                    const void* quotients, const void* points, const void* values, uint8_t* ok_out) {
     GG_CAPI_BEGIN
-    kzg_verify(true, n, kzg_g1, kzg_g2, digests, quotients, points, values, ok_out);
+    V::kzg_verify(true, n, kzg_g1, kzg_g2, digests, quotients, points, values, ok_out);
     GG_CAPI_END
 }
 extern "C" int gg_kzg_verify_bn254_host(size_t n, const void* kzg_g1, const void* kzg_g2, const void* digests,
                                         const void* quotients, const void* points, const void* values,
                                         uint8_t* ok_out) {
     GG_CAPI_BEGIN
-    kzg_verify(false, n, kzg_g1, kzg_g2, digests, quotients, points, values, ok_out);
+    V::kzg_verify(false, n, kzg_g1, kzg_g2, digests, quotients, points, values, ok_out);
     GG_CAPI_END
 }

@@ -257,6 +257,12 @@ def _load():
         "gg_plonk_verify_batch_host": ([P, S, P, P, HASH_FN, P, HASH_FN, P, P], I),
         "gg_kzg_verify_bn254": ([S, P, P, P, P, P, P, P], I),
         "gg_kzg_verify_bn254_host": ([S, P, P, P, P, P, P, P], I),
+        "gg_plonk_vk_create_bls12_381": ([ctypes.c_uint64, P, P, P, P, P, I, P, S, P, P, PP], I),
+        "gg_plonk_vk_destroy_bls12_381": ([P], I),
+        "gg_plonk_verify_batch_bls12_381": ([P, S, P, P, HASH_FN, P, HASH_FN, P, P], I),
+        "gg_plonk_verify_batch_bls12_381_host": ([P, S, P, P, HASH_FN, P, HASH_FN, P, P], I),
+        "gg_kzg_verify_bls12_381": ([S, P, P, P, P, P, P, P], I),
+        "gg_kzg_verify_bls12_381_host": ([S, P, P, P, P, P, P, P], I),
         "gg_profile_enable": ([I], I),
         "gg_profile_get": ([ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),
                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)], I),
@@ -337,6 +343,8 @@ EXPORTED = [
     "gg_groth16_vk_create_bls12_381", "gg_groth16_vk_destroy_bls12_381", "gg_groth16_verify_batch_bls12_381",
     "gg_groth16_verify_batch_bls12_381_host", "gg_hash_to_field_bls12_381", "gg_g1_check_endo_bls12_381",
     "gg_g2_check_endo_bls12_381",
+    "gg_plonk_vk_create_bls12_381", "gg_plonk_vk_destroy_bls12_381", "gg_plonk_verify_batch_bls12_381",
+    "gg_plonk_verify_batch_bls12_381_host", "gg_kzg_verify_bls12_381", "gg_kzg_verify_bls12_381_host",
 ]
 
 

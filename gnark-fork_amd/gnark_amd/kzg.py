@@ -1,8 +1,9 @@
 """KZG helpers: the Lagrange form of a canonical SRS on the GPU
 (kzg.ToLagrangeG1, backend/plonk/bls12-381/setup.go:134) over the C ABI's
 gg_kzg_to_lagrange_g1 (csrc/ecntt.hip: an inverse DFT over G1 points), and
-kzg.Verify for batches of BN254 openings (gg_kzg_verify_bn254,
-csrc/plonk_verify.hip)."""
+kzg.Verify for batches of openings over BN254 (gg_kzg_verify_bn254,
+csrc/plonk_verify.hip) or BLS12-381 (gg_kzg_verify_bls12_381,
+csrc/plonk_verify_bls.hip)."""
 from __future__ import annotations
 
 from . import fr
@@ -43,23 +44,32 @@ def to_lagrange_g1(points, log_n: int, curve: str = "bls12-381", out_device: boo
     return dst if out_device else bytes(dst)
 
 
-def verify(kzg_g1: bytes, kzg_g2: bytes, digests, quotients, points, values, host: bool = False) -> list:
-    """kzg.Verify of n independent BN254 openings under one SRS: one bool per
-    opening, e(C - y G + z H, G2) e(-H, [tau]G2) == 1.  kzg_g1: the SRS's G1
-    generator (64 B affine); kzg_g2: G2 and [tau]G2 (2 x 128 B); digests C and
-    quotients H: lists of 64-B affine points (all zero: the infinity); points z
-    and values y: integers.  host=True runs the same code on the CPU."""
+def verify(kzg_g1: bytes, kzg_g2: bytes, digests, quotients, points, values, host: bool = False,
+           curve: str = "bn254") -> list:
+    """kzg.Verify of n independent openings under one SRS: one bool per opening,
+    e(C - y G + z H, G2) e(-H, [tau]G2) == 1.  kzg_g1: the SRS's G1 generator
+    (one affine point: 64 B over BN254, 96 B over BLS12-381); kzg_g2: G2 and
+    [tau]G2 (2 x 128 B, 2 x 192 B); digests C and quotients H: lists of affine
+    points (all zero: the infinity); points z and values y: integers.  Over
+    BLS12-381 a digest or quotient outside the order-r subgroup gives False.
+    host=True runs the same code on the CPU."""
+    cid, pt, mont, _ = _curve(curve)
+    bls = cid == GG_CURVE_BLS12_381
+    r = fr.BLS_R if bls else fr.R
     n = len(digests)
     if not (n == len(quotients) == len(points) == len(values)):
         raise ValueError("digests, quotients, points and values must have one length")
-    if len(kzg_g1) < 64 or len(kzg_g2) != 256:
-        raise ValueError("kzg_g1: one G1Affine (64 bytes); kzg_g2: G2 and [tau]G2 (256 bytes)")
+    if len(kzg_g1) < pt or len(kzg_g2) != 4 * pt:
+        raise ValueError(f"kzg_g1: one G1Affine ({pt} bytes); kzg_g2: G2 and [tau]G2 ({4 * pt} bytes)")
     c, h = b"".join(bytes(x) for x in digests), b"".join(bytes(x) for x in quotients)
-    if len(c) != 64 * n or len(h) != 64 * n:
-        raise ValueError("a digest or a quotient is not a 64-byte affine point")
-    z = b"".join(fr.fr_mont(int(x) % fr.R) for x in points)
-    y = b"".join(fr.fr_mont(int(x) % fr.R) for x in values)
+    if len(c) != pt * n or len(h) != pt * n:
+        raise ValueError(f"a digest or a quotient is not a {pt}-byte affine point")
+    z = b"".join(mont(int(x) % r) for x in points)
+    y = b"".join(mont(int(x) % r) for x in values)
     ok = bytearray(n)
-    fn = lib.gg_kzg_verify_bn254_host if host else lib.gg_kzg_verify_bn254
-    check(fn(n, ptr(bytes(kzg_g1[:64])), ptr(bytes(kzg_g2)), ptr(c), ptr(h), ptr(z), ptr(y), ptr(ok)))
+    if bls:
+        fn = lib.gg_kzg_verify_bls12_381_host if host else lib.gg_kzg_verify_bls12_381
+    else:
+        fn = lib.gg_kzg_verify_bn254_host if host else lib.gg_kzg_verify_bn254
+    check(fn(n, ptr(bytes(kzg_g1[:pt])), ptr(bytes(kzg_g2)), ptr(c), ptr(h), ptr(z), ptr(y), ptr(ok)))
     return [bool(x) for x in ok]

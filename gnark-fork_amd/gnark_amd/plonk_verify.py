@@ -1,6 +1,9 @@
-"""PlonK Verify (backend/plonk/bn254/verify.go:45-294) for batches of BN254
-proofs under one verifying key, over the C ABI's gg_plonk_vk_create /
-gg_plonk_verify_batch (csrc/plonk_verify.hip).
+"""PlonK Verify (backend/plonk/bn254/verify.go:45-294 and its bls12-381 twin)
+for batches of proofs under one verifying key, over the C ABI's
+gg_plonk_vk_create / gg_plonk_verify_batch (BN254, csrc/plonk_verify.hip) and
+gg_plonk_vk_create_bls12_381 / gg_plonk_verify_batch_bls12_381 (BLS12-381,
+csrc/plonk_verify_bls.hip).  The key's class chooses the curve: VerifyingKey
+or Bls12381VerifyingKey.
 
 The transcripts (SHA-256 by default, or the caller's hashes) and the BSB22
 hashes run on the host inside the library; the point checks, PI(zeta), the
@@ -17,11 +20,12 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from . import fr, plonk_prover
-from ._lib import GG_CURVE_BN254, check, lib, ptr
+from ._lib import GG_CURVE_BLS12_381, GG_CURVE_BN254, check, lib, ptr
 
 VERIFY_OK, VERIFY_MALFORMED, VERIFY_QUOTIENT, VERIFY_KZG = 0, 1, 2, 3
 _VERIFY_MESSAGES = {
-    VERIFY_MALFORMED: "invalid proof: a point is not on the curve or a scalar is not reduced",
+    VERIFY_MALFORMED: "invalid proof: a point is not on the curve (BLS12-381: or not in the subgroup) or a scalar "
+                      "is not reduced",
     VERIFY_QUOTIENT: "claimed quotient is not as expected",  # verify.go:42
     VERIFY_KZG: "can't verify opening proof",                # gnark-crypto kzg.ErrVerifyOpeningProof
 }
@@ -44,7 +48,7 @@ class VerifyingKey:
 
     def __init__(self, vk: plonk_prover.VerifyingKey, kzg_g1: bytes, kzg_g2: bytes, curve: str = "bn254"):
         if curve != "bn254":
-            raise ValueError("PlonK Verify: curve must be 'bn254' (there is no BLS12-381 pairing yet)")
+            raise ValueError("VerifyingKey: curve must be 'bn254' (BLS12-381 keys: Bls12381VerifyingKey)")
         if len(kzg_g1) < 64 or len(kzg_g2) != 256:
             raise ValueError("kzg_g1: one G1Affine (64 bytes); kzg_g2: G2 and [tau]G2 (256 bytes)")
         self.vk = vk
@@ -71,26 +75,68 @@ class VerifyingKey:
             pass
 
 
-def _witness_bytes(w) -> bytes:
+class Bls12381VerifyingKey:
+    """The verifying key over BLS12-381 (gg_plonk_vk_create_bls12_381).  vk: the
+    plonk_prover.VerifyingKey of a BLS12-381 ProvingKey or of setup(); kzg_g1: the
+    SRS's G1 generator (96 B affine); kzg_g2: G2 and [tau]G2 (2 x 192 B affine).
+    Every G1 point of the key must lie in the order-r subgroup.  Creation runs on
+    the host alone; the first device batch uploads the key and its line tables."""
+    curve = "bls12-381"
+
+    def __init__(self, vk: plonk_prover.VerifyingKey, kzg_g1: bytes, kzg_g2: bytes):
+        if len(kzg_g1) < 96 or len(kzg_g2) != 384:
+            raise ValueError("kzg_g1: one G1Affine (96 bytes); kzg_g2: G2 and [tau]G2 (384 bytes)")
+        self.vk = vk
+        self.n_commitments, self.nb_public = len(vk.Qcp), vk.nb_public
+        idx = np.ascontiguousarray(list(vk.commitment_indexes), dtype=np.uint32)
+        h = ctypes.c_void_p()
+        nc = self.n_commitments
+        check(lib.gg_plonk_vk_create_bls12_381(
+            vk.size, ptr(fr.bls_fr_mont(vk.generator)), ptr(fr.bls_fr_mont(vk.coset_shift)),
+            ptr(b"".join(vk.S)), ptr(b"".join([vk.Ql, vk.Qr, vk.Qm, vk.Qo, vk.Qk])),
+            ptr(b"".join(vk.Qcp)) if nc else None, nc, ptr(idx) if nc else None, vk.nb_public,
+            ptr(bytes(kzg_g1[:96])), ptr(bytes(kzg_g2)), ctypes.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib.gg_plonk_vk_destroy_bls12_381(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _is_bls(vk) -> bool:
+    return isinstance(vk, Bls12381VerifyingKey)
+
+
+def _witness_bytes(w, bls: bool = False) -> bytes:
     """fr Montgomery bytes of a public witness given as bytes or as integers."""
     if isinstance(w, (bytes, bytearray, memoryview)):
         return bytes(w)
     if hasattr(w, "tobytes"):
         return w.tobytes()
+    if bls:
+        return b"".join(fr.bls_fr_mont(int(x) % fr.BLS_R) for x in w)
     return b"".join(fr.fr_mont(int(x) % fr.R) for x in w)
 
 
-def _proof_bytes(p, nc: int) -> bytes:
+def _proof_bytes(p, nc: int, curve: str = "bn254") -> bytes:
     if isinstance(p, plonk_prover.Proof):
         if len(p.bsb22) != nc:
             raise ValueError(f"the proof has {len(p.bsb22)} BSB22 commitments, the key has {nc}")
-        return plonk_prover.proof_bytes(p, "bn254")
+        return plonk_prover.proof_bytes(p, curve)
     return bytes(p)
 
 
-def verify_batch(proofs: Sequence, vk: VerifyingKey, witnesses: Sequence, challenge_hash: Optional[Callable] = None,
+def verify_batch(proofs: Sequence, vk, witnesses: Sequence, challenge_hash: Optional[Callable] = None,
                  folding_hash: Optional[Callable] = None, host: bool = False) -> list:
-    """plonk.Verify of every (proof, public witness) pair under vk: a list of
+    """plonk.Verify of every (proof, public witness) pair under vk (a VerifyingKey
+    or a Bls12381VerifyingKey: the key's class chooses the curve): a list of
     VERIFY_* statuses.  A proof is a plonk_prover.Proof or its bytes in the
     library's layout; a witness is the public inputs as fr Montgomery bytes or as
     integers; challenge_hash / folding_hash: hashlib constructors (default
@@ -99,9 +145,10 @@ def verify_batch(proofs: Sequence, vk: VerifyingKey, witnesses: Sequence, challe
     if n != len(witnesses):
         raise ValueError(f"{n} proofs, {len(witnesses)} witnesses")
     nc, nw = vk.n_commitments, vk.nb_public
-    size = lib.gg_plonk_proof_size_ex(GG_CURVE_BN254, nc)
-    wb = [_witness_bytes(w) for w in witnesses]
-    pb = [_proof_bytes(p, nc) for p in proofs]
+    bls = _is_bls(vk)
+    size = lib.gg_plonk_proof_size_ex(GG_CURVE_BLS12_381 if bls else GG_CURVE_BN254, nc)
+    wb = [_witness_bytes(w, bls) for w in witnesses]
+    pb = [_proof_bytes(p, nc, "bls12-381" if bls else "bn254") for p in proofs]
     for w in wb:
         if len(w) != 32 * nw:
             raise ValueError("invalid witness size")
@@ -111,12 +158,15 @@ def verify_batch(proofs: Sequence, vk: VerifyingKey, witnesses: Sequence, challe
     packed, wit = b"".join(pb), b"".join(wb)
     status = bytearray(n)
     hc, hf = plonk_prover._hash_cb(challenge_hash), plonk_prover._hash_cb(folding_hash)
-    fn = lib.gg_plonk_verify_batch_host if host else lib.gg_plonk_verify_batch
+    if bls:
+        fn = lib.gg_plonk_verify_batch_bls12_381_host if host else lib.gg_plonk_verify_batch_bls12_381
+    else:
+        fn = lib.gg_plonk_verify_batch_host if host else lib.gg_plonk_verify_batch
     check(fn(vk.handle, n, ptr(packed), ptr(wit) if nw else None, hc, None, hf, None, ptr(status)))
     return list(status)
 
 
-def verify(proof, vk: VerifyingKey, public_witness, challenge_hash: Optional[Callable] = None,
+def verify(proof, vk, public_witness, challenge_hash: Optional[Callable] = None,
            folding_hash: Optional[Callable] = None, host: bool = False) -> None:
     """plonk.Verify: returns None for a valid proof, raises VerifyError with
     gnark's message otherwise."""

@@ -1222,7 +1222,8 @@ int gg_g2_check_endo_bls12_381(size_t n, const void *g2, uint8_t *flags_out);
  * GG_ERR_INVALID_ARG, the message naming the offender: a null pointer, size not
  * a power of two >= 2, n_cmt < 0, a commitment index with nb_public + index >=
  * size, a key point off the curve, a G2 point at infinity, off the twist or
- * outside the r-torsion.  GG_ERR_UNSUPPORTED: curve != GG_CURVE_BN254. */
+ * outside the r-torsion.  GG_ERR_UNSUPPORTED: curve != GG_CURVE_BN254
+ * (BLS12-381 has gg_plonk_vk_create_bls12_381 below). */
 typedef struct gg_plonk_vk *gg_plonk_vk_t;
 int gg_plonk_vk_create(int curve, uint64_t size, const void *generator, const void *coset_shift, const void *S,
                        const void *Q, const void *Qcp, int n_cmt, const uint32_t *commitment_indexes,
@@ -1264,6 +1265,35 @@ int gg_kzg_verify_bn254(size_t n, const void *kzg_g1, const void *kzg_g2, const 
                         const void *points, const void *values, uint8_t *ok_out);
 int gg_kzg_verify_bn254_host(size_t n, const void *kzg_g1, const void *kzg_g2, const void *digests,
                              const void *quotients, const void *points, const void *values, uint8_t *ok_out);
+
+/* The same over BLS12-381 (backend/plonk/bls12-381/verify.go), with entry
+ * points of their own: the ones above stay BN254's.  Arguments as above with
+ * G1 points of 96 B (affine Montgomery, the infinity all zero), kzg_g2 = 2 x
+ * 192 B, scalars fr Montgomery of BLS12-381 (32 B), a proof of
+ * gg_plonk_proof_size_ex(GG_CURVE_BLS12_381, n_cmt) bytes in gg_plonk_prove's
+ * layout, the GG_PLONK_VERIFY_* statuses and the same lambda rule (RawBytes of a
+ * point: 96 B, the infinity 0x40 followed by zeros).
+ * G1 has a cofactor on this curve: every G1 point of the key must lie in the
+ * order-r subgroup (GG_ERR_INVALID_ARG "... is not in the r-torsion"), and a
+ * proof point on the curve but outside it gives GG_PLONK_VERIFY_MALFORMED, as
+ * gnark's decoder rejects it; in gg_kzg_verify_bls12_381 such a digest or
+ * quotient gives ok = 0.  The test is the endomorphism one of
+ * gg_g1_check_endo_bls12_381.  Key creation makes no device call. */
+typedef struct gg_plonk_vk_bls *gg_plonk_vk_bls_t;
+int gg_plonk_vk_create_bls12_381(uint64_t size, const void *generator, const void *coset_shift, const void *S,
+                                 const void *Q, const void *Qcp, int n_cmt, const uint32_t *commitment_indexes,
+                                 size_t nb_public, const void *kzg_g1, const void *kzg_g2, gg_plonk_vk_bls_t *out);
+int gg_plonk_vk_destroy_bls12_381(gg_plonk_vk_bls_t vk);
+int gg_plonk_verify_batch_bls12_381(gg_plonk_vk_bls_t vk, size_t n, const void *proofs, const void *public_witness,
+                                    gg_hash_fn challenge_hash, void *challenge_ctx, gg_hash_fn folding_hash,
+                                    void *folding_ctx, uint8_t *status_out);
+int gg_plonk_verify_batch_bls12_381_host(gg_plonk_vk_bls_t vk, size_t n, const void *proofs,
+                                         const void *public_witness, gg_hash_fn challenge_hash, void *challenge_ctx,
+                                         gg_hash_fn folding_hash, void *folding_ctx, uint8_t *status_out);
+int gg_kzg_verify_bls12_381(size_t n, const void *kzg_g1, const void *kzg_g2, const void *digests,
+                            const void *quotients, const void *points, const void *values, uint8_t *ok_out);
+int gg_kzg_verify_bls12_381_host(size_t n, const void *kzg_g1, const void *kzg_g2, const void *digests,
+                                 const void *quotients, const void *points, const void *values, uint8_t *ok_out);
 
 /* ------------------------------------------------------------ profiling
  * Kernel-level timing with HIP events recorded on the stream each kernel is
