@@ -1,8 +1,9 @@
 // The 8-bit fixed-base comb of batch.hip for a caller with many scalar vectors
 // for one base (Groth16 Setup: every G1 part is a multiple of the G1 generator):
 // the table is built once per generator and device-resident scalars are
-// multiplied into device-resident outputs.  Header only, included by
-// groth16_setup.hip alone; batch.hip keeps its own copy of the same method
+// multiplied into device-resident outputs.  Header only (the EC-NTT and the
+// setup from an SRS use its loads, stores and batch normalisation too);
+// batch.hip keeps its own copy of the same method
 // (gg_batch_scalar_mul: table, multiply and copy in one call) untouched.
 //   T[w][j] = j * 2^(8w) * B (32 x 256 affine points, built on the host);
 //   a scalar is 32 table lookups + 31 mixed XYZZ additions; the XYZZ results

@@ -33,6 +33,7 @@
 #include "field.cuh"
 #include "curve.cuh"
 #include "comb.h"
+#include "groth16_setup_common.h"
 #include "plonk_ops.h"
 #include <algorithm>
 #include <chrono>
@@ -50,120 +51,7 @@ namespace g16s {
 // occupancy is not the limit, the gathers are).  32 keeps the ONE wire of a 2^24 MiMC system
 // (5.6 M terms) at 5 rounds while the common 1..3-term wires cost one thread.
 constexpr uint32_t ACC_CHUNK = 32;
-constexpr uint32_t ACC_BLOCK = 256;
-// uint32 exclusive scan: 256 threads x 8 items per block
-constexpr uint32_t USCAN_PER = 8;
-constexpr uint32_t USCAN_BLK = 256 * USCAN_PER;
 
-// zeroed before it is freed (toxic waste / discrete logs)
-struct WipeBuf : DevBuf {
-    WipeBuf() = default;
-    explicit WipeBuf(size_t b) : DevBuf(b) {}
-    void wipe() {
-        if (p && bytes) {
-            (void)hipMemsetAsync(p, 0, bytes, hipStreamPerThread);
-            (void)hipStreamSynchronize(hipStreamPerThread);
-        }
-    }
-    void wipe_release() {
-        wipe();
-        release();
-    }
-    ~WipeBuf() { wipe(); }
-};
-
-// ---------------------------------------------------------------- uint32 scan
-// out[i] = sum of in[0..i) for i < m (in place allowed: a thread reads its own
-// items before it writes them); bsum[b] = the total of block b
-__global__ void __launch_bounds__(256) k_uscan_block(const uint32_t* in, uint32_t* out, size_t m, uint32_t* bsum) {
-    __shared__ uint32_t sh[256];
-    const size_t base = (size_t)blockIdx.x * USCAN_BLK + (size_t)threadIdx.x * USCAN_PER;
-    uint32_t v[USCAN_PER];
-    uint32_t s = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < USCAN_PER; k++) {
-        v[k] = base + k < m ? in[base + k] : 0u;
-        s += v[k];
-    }
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256; d <<= 1) {
-        const uint32_t add = threadIdx.x >= d ? sh[threadIdx.x - d] : 0u;
-        __syncthreads();
-        sh[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t run = sh[threadIdx.x] - s;  // exclusive prefix of this thread
-#pragma unroll
-    for (uint32_t k = 0; k < USCAN_PER; k++) {
-        if (base + k < m) out[base + k] = run;
-        run += v[k];
-    }
-    if (threadIdx.x == 255 && bsum) bsum[blockIdx.x] = sh[255];
-}
-__global__ void __launch_bounds__(256) k_uscan_add(uint32_t* out, size_t m, const uint32_t* boff) {
-    const size_t base = (size_t)(blockIdx.x + 1) * USCAN_BLK + (size_t)threadIdx.x * USCAN_PER;
-    const uint32_t c = boff[blockIdx.x + 1];
-#pragma unroll
-    for (uint32_t k = 0; k < USCAN_PER; k++)
-        if (base + k < m) out[base + k] += c;
-}
-// exclusive scan of in[0..m) into out[0..m); scratch from `tmp` (grow-only list)
-static void uscan(const uint32_t* in, uint32_t* out, size_t m, hipStream_t st, std::vector<std::unique_ptr<DevBuf>>& tmp) {
-    if (!m) return;
-    const size_t nblk = (m + USCAN_BLK - 1) / USCAN_BLK;
-    uint32_t* bsum = nullptr;
-    if (nblk > 1) {
-        tmp.emplace_back(new DevBuf(nblk * 4));
-        bsum = tmp.back()->as<uint32_t>();
-    }
-    hipLaunchKernelGGL(k_uscan_block, dim3((unsigned)nblk), dim3(256), 0, st, in, out, m, bsum);
-    GG_HIP(hipGetLastError());
-    if (nblk <= 1) return;
-    uscan(bsum, bsum, nblk, st, tmp);
-    hipLaunchKernelGGL(k_uscan_add, dim3((unsigned)(nblk - 1)), dim3(256), 0, st, out, m, (const uint32_t*)bsum);
-    GG_HIP(hipGetLastError());
-}
-
-// ---------------------------------------------------------------- transpose
-// key = side * n_wires + wire; row = 3 * constraint + side
-__global__ void __launch_bounds__(256) k_count(const uint32_t* off, const uint32_t* wire, uint32_t nrows, uint32_t nw,
-                                               uint32_t* cnt) {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= nrows) return;
-    const uint32_t side = r % 3u;
-    for (uint32_t t = off[r]; t < off[r + 1]; t++) atomicAdd(cnt + (size_t)side * nw + wire[t], 1u);
-}
-__global__ void __launch_bounds__(256) k_fill(const uint32_t* off, const uint32_t* wire, const uint32_t* cidx,
-                                              uint32_t nrows, uint32_t nw, const uint32_t* list_off, uint32_t* cursor,
-                                              uint2* ent) {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= nrows) return;
-    const uint32_t side = r % 3u, j = r / 3u;
-    for (uint32_t t = off[r]; t < off[r + 1]; t++) {
-        const size_t key = (size_t)side * nw + wire[t];
-        const uint32_t pos = list_off[key] + atomicAdd(cursor + key, 1u);
-        ent[pos] = make_uint2(j, cidx[t]);
-    }
-}
-
-// ---------------------------------------------------------------- accumulate
-// items still to add for key k after the previous round: the list length
-// (first) or the partials it wrote (none when it wrote its final sum)
-__device__ __forceinline__ uint32_t pending(const uint32_t* prev_off, uint32_t k, bool first) {
-    const uint32_t d = prev_off[k + 1] - prev_off[k];
-    return first ? d : (d > 1u ? d : 0u);
-}
-// work[k] = threads of this round for key k (k < nk), work[nk] = 0; *mx = max
-__global__ void __launch_bounds__(256) k_work(const uint32_t* prev_off, uint32_t nk, int first, uint32_t* work,
-                                              uint32_t* mx) {
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k > nk) return;
-    uint32_t w = 0;
-    if (k < nk) w = (pending(prev_off, k, first != 0) + ACC_CHUNK - 1) / ACC_CHUNK;
-    work[k] = w;
-    if (w > 1u) atomicMax(mx, w);
-}
 // thread i of nthr: the key whose [thr_off[k], thr_off[k + 1]) holds i, its
 // chunk c = i - thr_off[k]; adds at most ACC_CHUNK items.  A key with one thread
 // writes its final sum to out[key], the others partial i (so thr_off is also
@@ -334,21 +222,6 @@ static void layout(size_t nw, size_t nb_public, const uint32_t* cw, size_t nc, c
     }
 }
 
-template <class F>
-static F pow2k(F x, int k) {
-    for (int i = 0; i < k; i++) x = x * x;
-    return x;
-}
-
-struct Timer {
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    double lap() {
-        auto t1 = std::chrono::steady_clock::now();
-        double ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-        t0 = t1;
-        return ms;
-    }
-};
 
 }  // namespace g16s
 }  // namespace gg
@@ -359,18 +232,6 @@ using gg::comb::CombScratch;
 using gg::comb::CombTable;
 using gg::comb::comb_mul;
 
-struct gg_g16_setup {
-    int curve = 0, log_n = 0, device = 0;
-    size_t nw = 0, nA = 0, nB = 0, nK = 0, nZ = 0, n_vk = 0, g1b = 0, g2b = 0;
-    std::vector<size_t> n_ck, ck_base;
-    std::vector<uint32_t> k_wire_index;
-    size_t acc_launches = 0;
-    double ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    // points (public): G1 parts and G2 parts in HBM until read
-    DevBuf g1_A, g1_B, g1_K, g1_Z, vk_K, g1_abd /* alpha, beta, delta */, ck, ck_sigma;
-    DevBuf g2_B, g2_tail /* beta, delta, gamma, G, GRootSigmaNeg */;
-    DevBuf inf_a, inf_b;
-};
 
 namespace {
 
@@ -393,24 +254,9 @@ void run_setup(const SetupArgs& a, gg_g16_setup* h) {
     const size_t n = (size_t)1 << log_n;
     Layout lay;
     layout(a.nw, a.nb_public, a.cw, a.ncommit, a.coff, a.cwire, lay);
-    GG_CHECK(a.ncoef >= 1 && a.ncoef < 0xffffffffu, GG_ERR_INVALID_ARG, "empty coefficient table");
     const size_t nrows = 3 * a.ncons;
-    GG_CHECK(a.off[0] == 0, GG_ERR_INVALID_ARG, "term_off[0] must be 0");
-    for (size_t i = 0; i < nrows; i++)
-        GG_CHECK(a.off[i] <= a.off[i + 1], GG_ERR_INVALID_ARG, "term_off not monotonic");
-    const size_t nterms = a.off[nrows];
-    GG_CHECK(nterms == 0 || (a.wire && a.cidx), GG_ERR_INVALID_ARG, "null term arrays");
-    for (size_t t = 0; t < nterms; t++) {
-        if (a.wire[t] >= a.nw)
-            throw Error(GG_ERR_INVALID_ARG, "term " + std::to_string(t) + ": wire id " + std::to_string(a.wire[t]) +
-                                                " out of range (n_wires " + std::to_string(a.nw) + ")");
-        if (a.cidx[t] >= a.ncoef)
-            throw Error(GG_ERR_INVALID_ARG, "term " + std::to_string(t) + ": coefficient id " +
-                                                std::to_string(a.cidx[t]) + " out of range (n_coeffs " +
-                                                std::to_string(a.ncoef) + ")");
-    }
+    const size_t nterms = check_terms(a.nw, a.ncons, a.ncoef, a.off, a.wire, a.cidx);
     const size_t nk = 3 * a.nw;
-    GG_CHECK(nk + nterms < 0xfffffff0u, GG_ERR_INVALID_ARG, "system too large (3 n_wires + terms >= 2^32)");
     auto fe = [](const void* p) {
         F x;
         memcpy(&x, p, sizeof(F));
@@ -444,6 +290,7 @@ void run_setup(const SetupArgs& a, gg_g16_setup* h) {
     GG_HIP(hipGetDevice(&h->device));
     h->curve = std::is_same<FC, FrCfg>::value ? GG_CURVE_BN254 : GG_CURVE_BLS12_381;
     h->log_n = log_n;
+    h->acc_chunk = ACC_CHUNK;
     h->nw = a.nw;
     h->g1b = sizeof(Affine<G1F>);
     h->g2b = sizeof(Affine<G2F>);
@@ -528,56 +375,23 @@ void run_setup(const SetupArgs& a, gg_g16_setup* h) {
     WipeBuf abc(nk * 32);
     zero(abc);
     {
-        struct Ev {  // destroyed on the error paths too
-            hipEvent_t e = nullptr;
-            Ev() { GG_HIP(hipEventCreate(&e)); }
-            ~Ev() { (void)hipEventDestroy(e); }
-        } ev0, ev1;
-        hipEvent_t e0 = ev0.e, e1 = ev1.e;
-        DevBuf work((nk + 1) * 4), offA((nk + 1) * 4), offB((nk + 1) * 4), mx(16);
-        WipeBuf pa, pb;
-        const uint32_t* prev_off = u32(list_off);
-        uint32_t* thr_off = u32(offA);
-        WipeBuf* psrc = &pa;
-        WipeBuf* pdst = &pb;
-        float acc_ms = 0;
-        for (int round = 0;; round++) {
-            GG_CHECK(round < 8, GG_ERR_INTERNAL, "accumulate: too many rounds");  // 32^7 > 2^32 entries
-            zero(mx);
-            hipLaunchKernelGGL(k_work, dim3(grid_for(nk + 1, 256)), dim3(256), 0, st, prev_off, (uint32_t)nk,
-                               round == 0 ? 1 : 0, u32(work), u32(mx));
-            GG_HIP(hipGetLastError());
-            uscan(u32(work), thr_off, nk + 1, st, tmp);
-            const uint32_t nthr = rd32(thr_off + nk);
-            const uint32_t maxw = rd32(u32(mx));
-            if (nthr == 0) break;
-            pdst->wipe_release();
-            if (maxw > 1) pdst->alloc((size_t)nthr * 32);
-            GG_HIP(hipEventRecord(e0, st));
-            if (round == 0)
-                hipLaunchKernelGGL((k_acc<F, true>), dim3(grid_for(nthr, ACC_BLOCK)), dim3(ACC_BLOCK), 0, st, prev_off,
-                                   (const uint32_t*)thr_off, (uint32_t)nk, nthr, (const uint2*)ent.p,
-                                   (const F*)Ltab.p, (const F*)d_coef.p, (const F*)nullptr, pdst->as<F>(),
-                                   abc.as<F>());
-            else
-                hipLaunchKernelGGL((k_acc<F, false>), dim3(grid_for(nthr, ACC_BLOCK)), dim3(ACC_BLOCK), 0, st,
-                                   prev_off, (const uint32_t*)thr_off, (uint32_t)nk, nthr, (const uint2*)nullptr,
-                                   (const F*)nullptr, (const F*)nullptr, (const F*)psrc->p, pdst->as<F>(),
-                                   abc.as<F>());
-            GG_HIP(hipGetLastError());
-            GG_HIP(hipEventRecord(e1, st));
-            GG_WAIT_STREAM(st);
-            float ms = 0;
-            GG_HIP(hipEventElapsedTime(&ms, e0, e1));
-            acc_ms += ms;
-            h->acc_launches++;
-            h->ms[7] += nthr;
-            if (maxw <= 1) break;
-            std::swap(psrc, pdst);
-            prev_off = thr_off;
-            thr_off = thr_off == u32(offA) ? u32(offB) : u32(offA);
-        }
-        h->ms[6] = acc_ms;
+        AccStats stats;
+        acc_rounds<ACC_CHUNK>(
+            u32(list_off), nk, 32, st, tmp, stats,
+            [&](bool first, const uint32_t* prev_off, const uint32_t* thr_off, uint32_t nthr, const void* psrc,
+                void* pdst) {
+                if (first)
+                    hipLaunchKernelGGL((k_acc<F, true>), dim3(grid_for(nthr, ACC_BLOCK)), dim3(ACC_BLOCK), 0, st, prev_off,
+                                       thr_off, (uint32_t)nk, nthr, (const uint2*)ent.p, (const F*)Ltab.p,
+                                       (const F*)d_coef.p, (const F*)nullptr, (F*)pdst, abc.as<F>());
+                else
+                    hipLaunchKernelGGL((k_acc<F, false>), dim3(grid_for(nthr, ACC_BLOCK)), dim3(ACC_BLOCK), 0, st,
+                                       prev_off, thr_off, (uint32_t)nk, nthr, (const uint2*)nullptr, (const F*)nullptr,
+                                       (const F*)nullptr, (const F*)psrc, (F*)pdst, abc.as<F>());
+            });
+        h->acc_launches = stats.launches;
+        h->ms[6] = stats.kernel_ms;
+        h->ms[7] = stats.threads;
         h->ms[8] = (double)nterms;
     }
     Ltab.wipe_release();
@@ -748,7 +562,7 @@ extern "C" int gg_groth16_setup_info(gg_g16_setup_t h, int* log_n, size_t* nA, s
     if (n_commitments) *n_commitments = h->n_ck.size();
     if (n_ck)
         for (size_t j = 0; j < std::min(n_ck_cap, h->n_ck.size()); j++) n_ck[j] = h->n_ck[j];
-    if (acc_chunk) *acc_chunk = ACC_CHUNK;
+    if (acc_chunk) *acc_chunk = h->acc_chunk;
     if (acc_launches) *acc_launches = h->acc_launches;
     GG_CAPI_END
 }
@@ -813,7 +627,7 @@ extern "C" int gg_groth16_setup_read(gg_g16_setup_t h, int which, void* out_host
 extern "C" int gg_groth16_setup_timings(gg_g16_setup_t h, double* ms, int n) {
     GG_CAPI_BEGIN
     GG_CHECK(h && ms, GG_ERR_INVALID_ARG, "null argument");
-    for (int i = 0; i < std::min(n, 9); i++) ms[i] = h->ms[i];
+    for (int i = 0; i < std::min(n, GG_SETUP_TIMING_SLOTS); i++) ms[i] = h->ms[i];
     GG_CAPI_END
 }
 

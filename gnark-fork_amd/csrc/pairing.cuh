@@ -709,6 +709,14 @@ inline GG_HDN FpBls inv_call(const FpBls& a) {
     }
     return acc.v;
 }
+// 1 / a over Called<Fp2Bls>: the norm's inverse by inv_call (the batch normalisations of
+// ecntt_g2.hip and groth16_mpc_setup.hip)
+inline GG_HDN Called<Fp2Bls> inverse(const Called<Fp2Bls>& a) {
+    using C = Called<FpBls>;
+    const C a0{a.v.a0}, a1{a.v.a1};
+    const C ni{inv_call((sqr(a0) + sqr(a1)).v)};
+    return Called<Fp2Bls>{Fp2Bls{(a0 * ni).v, (-(a1 * ni)).v}};
+}
 template <class Tw, class FF>
 GG_HDN bool times_r_is_inf(const Affine<FF>& q) {
     using C = typename std::conditional<Tw::CALLED_POINT_OPS, Called<FF>, FF>::type;

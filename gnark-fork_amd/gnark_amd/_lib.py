@@ -39,6 +39,7 @@ GG_GT_BYTES_BLS12_381 = 576
 GG_VERIFY_MAX_K = 1024
 GG_PLONK_VERIFY_OK, GG_PLONK_VERIFY_MALFORMED, GG_PLONK_VERIFY_QUOTIENT, GG_PLONK_VERIFY_KZG = 0, 1, 2, 3
 GG_PLONK_SETUP_TIMING_SLOTS = 10
+GG_SETUP_TIMING_SLOTS = 24
 
 
 # gg_exchange_fn (include/gnark_amd.h): all-to-all supplied by the caller
@@ -221,6 +222,9 @@ def _load():
         "gg_groth16_setup_timings": ([P, ctypes.POINTER(ctypes.c_double), I], I),
         "gg_groth16_setup_release": ([P], I),
         "gg_kzg_to_lagrange_g1": ([I, I, P, P, I, P, I, P], I),
+        "gg_kzg_to_lagrange_g2": ([I, I, P, P, I, P, I, P], I),
+        "gg_groth16_setup_from_srs": ([I, S, S, S, P, P, P, P, S, P, I, P, I, P, I, P, I, P, I, S, I, P, P, P, PP], I),
+        "gg_groth16_setup_contribute": ([P, P], I),
         "gg_plonk_setup_sizes": ([S, S, ctypes.POINTER(I), ctypes.POINTER(I)], I),
         "gg_plonk_setup": ([I, S, S, S, P, P, P, S, I, P, P, P, P, P, P, S, P, PP], I),
         "gg_plonk_setup_info": ([P, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I),
@@ -331,7 +335,8 @@ EXPORTED = [
     "gg_wait_selftest", "gg_wait_selftest_device", "gg_task_selftest", "gg_release_task_queues",
     "gg_hint_supported", "gg_hint_eval_host", "gg_r1cs_set_hints", "gg_scs_set_hints",
     "gg_groth16_setup_layout", "gg_groth16_setup", "gg_groth16_setup_info", "gg_groth16_setup_read",
-    "gg_groth16_setup_timings", "gg_groth16_setup_release",
+    "gg_groth16_setup_timings", "gg_groth16_setup_release", "gg_groth16_setup_from_srs",
+    "gg_groth16_setup_contribute", "gg_kzg_to_lagrange_g2",
     "gg_kzg_to_lagrange_g1", "gg_plonk_setup_sizes", "gg_plonk_setup", "gg_plonk_setup_info", "gg_plonk_setup_read",
     "gg_plonk_setup_timings", "gg_plonk_setup_pk", "gg_plonk_setup_release",
     "gg_pairing_bn254", "gg_pairing_check_bn254", "gg_pairing_bn254_host", "gg_g1_check_bn254", "gg_g2_check_bn254",

@@ -893,6 +893,41 @@ def setup_device(nb_public: int, n_wires: int, term_off, term_wire, term_coeff, 
     return SetupResult(h, curve)
 
 
+def read_keys(res: SetupResult, n_wires: int, nb_public: int, commitments=()):
+    """(ProvingKeyData, VerifyingKeyData) of a setup handle, part by part
+    (gg_groth16_setup_read): the read-back of `setup` and of mpcsetup.Phase2.extract_keys."""
+    from . import _lib as L
+    from . import pedersen as ped
+    curve = res.curve
+    g1b, g2b = _SIZES[curve]
+    rd = res.read
+    keys = None
+    if res.n_commitments:
+        keys = [ped.ProvingKey(rd(L.GG_SETUP_CK_BASIS + j, m * g1b), rd(L.GG_SETUP_CK_BASIS_SIGMA + j, m * g1b))
+                for j, m in enumerate(res.n_ck)]
+    kidx = np.frombuffer(rd(L.GG_SETUP_K_WIRE_INDEX, 4 * res.nK), dtype=np.uint32)
+    alpha1, beta1, delta1 = (rd(w, g1b) for w in (L.GG_SETUP_ALPHA1, L.GG_SETUP_BETA1, L.GG_SETUP_DELTA1))
+    beta2, delta2, gamma2 = (rd(w, g2b) for w in (L.GG_SETUP_BETA2, L.GG_SETUP_DELTA2, L.GG_SETUP_GAMMA2))
+    pk = ProvingKeyData(
+        log_n=res.log_n, g1_A=rd(L.GG_SETUP_G1_A, res.nA * g1b), g1_B=rd(L.GG_SETUP_G1_B, res.nB * g1b),
+        g1_Z=rd(L.GG_SETUP_G1_Z, res.nZ * g1b), g1_K=rd(L.GG_SETUP_G1_K, res.nK * g1b),
+        alpha1=alpha1, beta1=beta1, delta1=delta1, g2_B=rd(L.GG_SETUP_G2_B, res.nB * g2b),
+        beta2=beta2, delta2=delta2, infinity_A=rd(L.GG_SETUP_INFINITY_A, n_wires),
+        infinity_B=rd(L.GG_SETUP_INFINITY_B, n_wires), nb_public=nb_public,
+        k_wire_index=kidx if res.n_commitments else None, curve=curve, commitment_keys=keys)
+    vk = VerifyingKeyData(alpha1=alpha1, beta1=beta1, delta1=delta1, beta2=beta2, gamma2=gamma2, delta2=delta2,
+                          K=rd(L.GG_SETUP_VK_K, res.n_vk_k * g1b), nb_public=nb_public, curve=curve)
+    if res.n_commitments:
+        pv = rd(L.GG_SETUP_PEDERSEN_VK, 2 * g2b)
+        vk.commitment_key_g, vk.commitment_key_g_root_sigma_neg = pv[:g2b], pv[g2b:]
+        # GetPublicAndCommitmentCommitted(commitmentWires, nbPublic) (commitment.go:53-74):
+        # public wires as they are, a committed commitment wire as its position after them
+        cws = [int(c[0]) for c in commitments]
+        vk.public_and_commitment_committed = [
+            [int(w) if w < nb_public else nb_public + cws.index(int(w)) for w in c[2]] for c in commitments]
+    return pk, vk
+
+
 def setup(nb_public: int, n_wires: int, term_off, term_wire, term_coeff, coeffs: Sequence[int],
           commitments=(), toxic_waste: Optional[ToxicWaste] = None, pedersen=None, curve: str = "bn254"):
     """groth16.Setup (setup.go:85-337) on the GPU -> (ProvingKeyData, VerifyingKeyData).
@@ -902,47 +937,17 @@ def setup(nb_public: int, n_wires: int, term_off, term_wire, term_coeff, coeffs:
     per BSB22 commitment; toxic_waste / pedersen = (sigma, g) pin the randomness
     (tests), otherwise they are sampled with `secrets`, zero rejected, as
     sampleToxicWaste does.  The ProvingKeyData goes straight into ProvingKey(...)."""
-    from . import _lib as L
-    from . import pedersen as ped
     res = setup_device(nb_public, n_wires, term_off, term_wire, term_coeff, coeffs, commitments, toxic_waste,
                        pedersen, curve)
     try:
-        g1b, g2b = _SIZES[curve]
-        rd = res.read
-        keys = None
-        if res.n_commitments:
-            keys = [ped.ProvingKey(rd(L.GG_SETUP_CK_BASIS + j, m * g1b), rd(L.GG_SETUP_CK_BASIS_SIGMA + j, m * g1b))
-                    for j, m in enumerate(res.n_ck)]
-        kidx = np.frombuffer(rd(L.GG_SETUP_K_WIRE_INDEX, 4 * res.nK), dtype=np.uint32)
-        alpha1, beta1, delta1 = (rd(w, g1b) for w in (L.GG_SETUP_ALPHA1, L.GG_SETUP_BETA1, L.GG_SETUP_DELTA1))
-        beta2, delta2, gamma2 = (rd(w, g2b) for w in (L.GG_SETUP_BETA2, L.GG_SETUP_DELTA2, L.GG_SETUP_GAMMA2))
-        pk = ProvingKeyData(
-            log_n=res.log_n, g1_A=rd(L.GG_SETUP_G1_A, res.nA * g1b), g1_B=rd(L.GG_SETUP_G1_B, res.nB * g1b),
-            g1_Z=rd(L.GG_SETUP_G1_Z, res.nZ * g1b), g1_K=rd(L.GG_SETUP_G1_K, res.nK * g1b),
-            alpha1=alpha1, beta1=beta1, delta1=delta1, g2_B=rd(L.GG_SETUP_G2_B, res.nB * g2b),
-            beta2=beta2, delta2=delta2, infinity_A=rd(L.GG_SETUP_INFINITY_A, n_wires),
-            infinity_B=rd(L.GG_SETUP_INFINITY_B, n_wires), nb_public=nb_public,
-            k_wire_index=kidx if res.n_commitments else None, curve=curve, commitment_keys=keys)
-        vk = VerifyingKeyData(alpha1=alpha1, beta1=beta1, delta1=delta1, beta2=beta2, gamma2=gamma2, delta2=delta2,
-                              K=rd(L.GG_SETUP_VK_K, res.n_vk_k * g1b), nb_public=nb_public, curve=curve)
-        if res.n_commitments:
-            pv = rd(L.GG_SETUP_PEDERSEN_VK, 2 * g2b)
-            vk.commitment_key_g, vk.commitment_key_g_root_sigma_neg = pv[:g2b], pv[g2b:]
-            # GetPublicAndCommitmentCommitted(commitmentWires, nbPublic) (commitment.go:53-74):
-            # public wires as they are, a committed commitment wire as its position after them
-            cws = [int(c[0]) for c in commitments]
-            vk.public_and_commitment_committed = [
-                [int(w) if w < nb_public else nb_public + cws.index(int(w)) for w in c[2]] for c in commitments]
-        return pk, vk
+        return read_keys(res, n_wires, nb_public, commitments)
     finally:
         res.close()
 
 
-def setup_from_terms(nb_public: int, n_wires: int, constraints, **kw):
-    """setup for [(L, R, O)] constraint lists with L = [(wire, coeff int), ...]
-    (solver.R1CS.from_terms' input)."""
-    curve = kw.get("curve", "bn254")
-    mod = fr.R if curve == "bn254" else fr.BLS_R
+def terms_to_csr(constraints, mod: int):
+    """(term_off, term_wire, term_coeff, table) of [(L, R, O)] constraint lists with
+    L = [(wire, coeff int), ...]; coefficients are numbered by first appearance."""
     table, index = [], {}
     off, wires, cids = [0], [], []
     for sides in constraints:
@@ -955,7 +960,15 @@ def setup_from_terms(nb_public: int, n_wires: int, constraints, **kw):
                 wires.append(w)
                 cids.append(index[k])
             off.append(len(wires))
-    return setup(nb_public, n_wires, off, wires, cids, table or [1], **kw)
+    return off, wires, cids, table or [1]
+
+
+def setup_from_terms(nb_public: int, n_wires: int, constraints, **kw):
+    """setup for [(L, R, O)] constraint lists with L = [(wire, coeff int), ...]
+    (solver.R1CS.from_terms' input)."""
+    curve = kw.get("curve", "bn254")
+    off, wires, cids, table = terms_to_csr(constraints, fr.R if curve == "bn254" else fr.BLS_R)
+    return setup(nb_public, n_wires, off, wires, cids, table, **kw)
 
 
 # ------------------------------------------------------------------- Verify

@@ -1,6 +1,8 @@
 """KZG helpers: the Lagrange form of a canonical SRS on the GPU
 (kzg.ToLagrangeG1, backend/plonk/bls12-381/setup.go:134) over the C ABI's
-gg_kzg_to_lagrange_g1 (csrc/ecntt.hip: an inverse DFT over G1 points), and
+gg_kzg_to_lagrange_g1 (csrc/ecntt.hip: an inverse DFT over G1 points), the same
+over G2 (gg_kzg_to_lagrange_g2, csrc/ecntt_g2.hip: lagrangeCoeffsG2 of
+backend/groth16/bn254/mpcsetup/lagrange.go), and
 kzg.Verify for batches of openings over BN254 (gg_kzg_verify_bn254,
 csrc/plonk_verify.hip) or BLS12-381 (gg_kzg_verify_bls12_381,
 csrc/plonk_verify_bls.hip)."""
@@ -18,18 +20,13 @@ def _curve(curve: str):
     raise ValueError("curve must be 'bls12-381' or 'bn254'")
 
 
-def to_lagrange_g1(points, log_n: int, curve: str = "bls12-381", out_device: bool = False, omega: int = None,
-                   out=None):
-    """[L_i(tau)]G, i < n = 2^log_n, from points = [tau^j]G, j < n (affine, the
-    curve's layout; bytes or a DeviceBuffer).  out[i] = (1/n) sum_j omega^(-ij)
-    points[j] for any input points.  Returns bytes, or a DeviceBuffer with
-    out_device; `out` (a DeviceBuffer, possibly `points` itself) receives the
-    result in place of a new buffer.  omega: the domain's generator (default
-    gnark-crypto's fft.NewDomain choice)."""
+def _to_lagrange(fn, scale: int, points, log_n, curve, out_device, omega, out):
+    """to_lagrange_g1 / _g2: `scale` G1 point sizes per point."""
     cid, pt, mont, gen = _curve(curve)
     if not 1 <= log_n <= 27:
         raise ValueError("log_n must be in 1 .. 27")
     w = mont(omega if omega is not None else gen(log_n))
+    pt *= scale
     nbytes = pt << log_n
     in_dev = isinstance(points, DeviceBuffer)
     if not in_dev:
@@ -40,8 +37,26 @@ def to_lagrange_g1(points, log_n: int, curve: str = "bls12-381", out_device: boo
         dst, out_device = out, True
     else:
         dst = DeviceBuffer(nbytes) if out_device else bytearray(nbytes)
-    check(lib.gg_kzg_to_lagrange_g1(cid, log_n, ptr(w), ptr(points), int(in_dev), ptr(dst), int(out_device), None))
+    check(fn(cid, log_n, ptr(w), ptr(points), int(in_dev), ptr(dst), int(out_device), None))
     return dst if out_device else bytes(dst)
+
+
+def to_lagrange_g1(points, log_n: int, curve: str = "bls12-381", out_device: bool = False, omega: int = None,
+                   out=None):
+    """[L_i(tau)]G, i < n = 2^log_n, from points = [tau^j]G, j < n (affine, the
+    curve's layout; bytes or a DeviceBuffer).  out[i] = (1/n) sum_j omega^(-ij)
+    points[j] for any input points.  Returns bytes, or a DeviceBuffer with
+    out_device; `out` (a DeviceBuffer, possibly `points` itself) receives the
+    result in place of a new buffer.  omega: the domain's generator (default
+    gnark-crypto's fft.NewDomain choice)."""
+    return _to_lagrange(lib.gg_kzg_to_lagrange_g1, 1, points, log_n, curve, out_device, omega, out)
+
+
+def to_lagrange_g2(points, log_n: int, curve: str = "bls12-381", out_device: bool = False, omega: int = None,
+                   out=None):
+    """to_lagrange_g1 over G2 points (128 B on bn254, 192 B on bls12-381):
+    [tau^j]2 -> [L_i(tau)]2, the pk.G2.B side of mpcsetup.init_phase2."""
+    return _to_lagrange(lib.gg_kzg_to_lagrange_g2, 2, points, log_n, curve, out_device, omega, out)
 
 
 def verify(kzg_g1: bytes, kzg_g2: bytes, digests, quotients, points, values, host: bool = False,

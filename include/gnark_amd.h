@@ -964,9 +964,77 @@ int gg_groth16_setup_read(gg_g16_setup_t h, int which, void *out_host, size_t by
  * compaction, 4 G1 points, 5 G2 points, 6 accumulate kernels only (device time
  * between events); then two counts: 7 the accumulation's threads over all its
  * rounds (each adds <= *acc_chunk items and writes one 32-B sum), 8 the terms;
- * writes min(n, 9) values */
+ * writes min(n, GG_SETUP_TIMING_SLOTS) values.  A key from
+ * gg_groth16_setup_from_srs fills the same nine (1 = the four EC-NTTs, 3 = K, Z,
+ * flags and compaction, 4 / 5 = the G1 / G2 normalisations, 6 / 7 summed over its
+ * three accumulations, a thread writing one XYZZ sum) and, from slot 9 on, its
+ * own phases: 9..12 the EC-NTT of tau_g1, alpha_tau_g1, beta_tau_g1, tau_g2;
+ * 13 upload and point checks; then per accumulation (G1 over [L_j]1 -> A, B, C;
+ * G1 over [beta L_j]1 / [alpha L_j]1 -> K's other two sums; G2 -> pk.G2.B) the
+ * general-term multiplications and the rounds, device time between events:
+ * 14 / 15, 16 / 17, 18 / 19; 20 Z; 21 the normalisations; 22 the last
+ * gg_groth16_setup_contribute; 23 a count, the general terms. */
+#define GG_SETUP_TIMING_SLOTS 24
 int gg_groth16_setup_timings(gg_g16_setup_t h, double *ms, int n);
 int gg_groth16_setup_release(gg_g16_setup_t h);
+
+/* ------------------------------------------------------------ Groth16 MPC setup, phase 2
+ * InitPhase2 + ExtractKeys (backend/groth16/bn254/mpcsetup/phase2.go:53-179,
+ * setup.go:25-97, the same files under bls12-381/) on the GPU: a Groth16 key from
+ * a phase-1 SRS (powers of tau) instead of the toxic waste.  The R1CS exactly as
+ * gg_groth16_setup takes it; coefficients are classified by VALUE (0, 1, 2, -1 are
+ * skips and additions as in accumulateG1 / accumulateG2, phase2.go:62-100, any
+ * other value is one scalar multiplication): this ABI reserves no coefficient ids.
+ * n_commitments is not a parameter: a circuit with BSB22 commitments is not
+ * representable, as in the reference, whose ExtractKeys has no commitment keys.
+ *
+ * The phase-1 parameters (phase1.go:35-50), affine in the curve's layout, each in
+ * host memory or in HBM (its *_on_device flag):
+ *   tau_g1        [tau^i]1, i < 2 srs_n - 1     alpha_tau_g1  [alpha tau^i]1, i < srs_n
+ *   beta_tau_g1   [beta tau^i]1, i < srs_n      tau_g2        [tau^i]2, i < srs_n
+ *   beta_g2       [beta]2
+ * The domain is n = the next power of two of n_constraints (fft.NewDomain,
+ * setup.go:29).  The reference takes len(AlphaTau) as the domain (phase2.go:55,
+ * 103-106) and so works only when srs_n == n; here any power of two srs_n >= n
+ * is accepted and the prefixes are used (tau_g1[0 .. 2n - 2], the first n of the
+ * others), so that one ceremony file serves many circuits.
+ *
+ * The result is a gg_g16_setup_t: gg_groth16_setup_info / _read / _timings /
+ * _release and every GG_SETUP_* part work on it (no Pedersen parts).  GAMMA2 is
+ * g2_gen (setup.go:88), ALPHA1 / BETA1 are alpha_tau_g1[0] / beta_tau_g1[0]
+ * (setup.go:30-31), BETA2 is beta_g2 (setup.go:37), DELTA1 / DELTA2 start as the
+ * generators (phase2.go:142-144).  G1_Z: tau_g1[i + n] - tau_g1[i], i <= n - 2,
+ * bit-reversed over n slots and truncated to n - 1 (phase2.go:148-154; the second
+ * bitReverse of setup.go:34 runs over n - 1 elements, an odd length, and moves
+ * nothing), the layout of gg_groth16_setup.  Infinity flags and the compaction of
+ * A / B / G2.B are by value (setup.go:40-80).  *acc_chunk of the info is the
+ * chunk of the point accumulation.  With gamma = 1 the key equals, byte for byte,
+ * the one gg_groth16_setup makes from (tau, alpha, beta, 1, delta).
+ *
+ * GG_ERR_INVALID_ARG before any device call, the message naming the offender: a
+ * null argument, srs_n not a power of two or below n, a term wire >= n_wires or
+ * a coefficient id >= n_coeffs, omega not of order n, nb_public > n_wires.
+ * check_points != 0 runs the point and subgroup checks (gg_g1_check_bn254 /
+ * gg_g2_check_bn254, the endomorphism tests on BLS12-381) over the used prefixes
+ * and returns GG_ERR_INVALID_ARG naming the array and the first bad index; it
+ * also refuses an infinity at tau_g1[1], tau_g2[1], alpha_tau_g1[0],
+ * beta_tau_g1[0] or beta_g2.  That the SRS is a well-formed powers-of-tau string
+ * is NOT checked: VerifyPhase1 (phase1.go:120-179) is the ceremony's job. */
+int gg_groth16_setup_from_srs(int curve, size_t n_wires, size_t n_constraints, size_t nb_public,
+                              const uint32_t *term_off, const uint32_t *term_wire, const uint32_t *term_coeff,
+                              const void *coeffs, size_t n_coeffs, const void *tau_g1, int tau_g1_on_device,
+                              const void *alpha_tau_g1, int alpha_tau_g1_on_device, const void *beta_tau_g1,
+                              int beta_tau_g1_on_device, const void *tau_g2, int tau_g2_on_device,
+                              const void *beta_g2, int beta_g2_on_device, size_t srs_n, int check_points,
+                              const void *omega_mont, const void *g1_gen, const void *g2_gen,
+                              gg_g16_setup_t *out);
+/* One delta contribution (Phase2.Contribute, phase2.go:181-210, the point updates
+ * only: the public key and the hashes stay with the ceremony): DELTA1 and DELTA2
+ * are multiplied by delta (fr Montgomery), every point of G1_Z and G1_K by
+ * delta^-1, on the device.  May be called repeatedly; the effects multiply.
+ * GG_ERR_INVALID_ARG: delta = 0, a null handle, a handle from gg_groth16_setup.
+ * The device copies of delta and delta^-1 are zeroed before they are freed. */
+int gg_groth16_setup_contribute(gg_g16_setup_t h, const void *delta);
 
 /* ------------------------------------------------------------ PlonK Setup
  * plonk.Setup (backend/plonk/bls12-381/setup.go:108-171, the same file under
@@ -984,6 +1052,11 @@ int gg_groth16_setup_release(gg_g16_setup_t h);
  * argument, log_n out of range, omega^(n/2) != -1, an unknown curve. */
 int gg_kzg_to_lagrange_g1(int curve, int log_n, const void *omega_mont, const void *g1_in, int in_on_device,
                           void *g1_out, int out_on_device, void *hip_stream);
+/* The same over G2 points (lagrangeCoeffsG2, backend/groth16/bn254/mpcsetup/
+ * lagrange.go:43-58 and phase2.go:104: [tau^j]2 -> [L_i(tau)]2), argument for
+ * argument: 128 B per point on GG_CURVE_BN254, 192 B on GG_CURVE_BLS12_381. */
+int gg_kzg_to_lagrange_g2(int curve, int log_n, const void *omega_mont, const void *g2_in, int in_on_device,
+                          void *g2_out, int out_on_device, void *hip_stream);
 
 typedef struct gg_plonk_setup *gg_plonk_setup_t;
 /* initDomains (setup.go:275-290), host only: sizeSystem = n_constraints +
