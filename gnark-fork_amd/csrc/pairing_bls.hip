@@ -46,21 +46,6 @@ __global__ void __launch_bounds__(64) k_g2_check_bls(size_t n, const G2B* q, uin
     if (i < n) flags[i] = (uint8_t)g2_check<TwB>(q[i]);
 }
 
-static void run_pairing_bls(size_t n, int k, const void* g1, const void* g2, void* gt_out, uint8_t* ok_out) {
-    Stream st;
-    DevBuf b1, b2;
-    const size_t np = n * (size_t)k;
-    const G1B* d1 = (const G1B*)to_device(g1, np * sizeof(G1B), b1, st.s);
-    const G2B* d2 = (const G2B*)to_device(g2, np * sizeof(G2B), b2, st.s);
-    OutBuf o;
-    if (gt_out) o.init(gt_out, n * sizeof(GTB));
-    else o.init(ok_out, n);
-    hipLaunchKernelGGL(k_pairing_bls, dim3(grid_for(n, 64)), dim3(64), 0, st.s, n, k, d1, d2,
-                       gt_out ? (GTB*)o.dev : nullptr, gt_out ? nullptr : (uint8_t*)o.dev);
-    GG_HIP(hipGetLastError());
-    o.finish(st.s);
-}
-
 }  // namespace pairing
 }  // namespace gg
 
@@ -70,13 +55,13 @@ using namespace gg::pairing;
 extern "C" int gg_pairing_bls12_381(size_t n, int k, const void* g1, const void* g2, void* gt_out) {
     GG_CAPI_BEGIN
     check_pairing_args(n, k, g1, g2, gt_out, "gt_out");
-    run_pairing_bls(n, k, g1, g2, gt_out, nullptr);
+    run_pairing<GTB, G1B, G2B>(k_pairing_bls, n, k, g1, g2, gt_out, nullptr);
     GG_CAPI_END
 }
 extern "C" int gg_pairing_check_bls12_381(size_t n, int k, const void* g1, const void* g2, uint8_t* ok_out) {
     GG_CAPI_BEGIN
     check_pairing_args(n, k, g1, g2, ok_out, "ok_out");
-    run_pairing_bls(n, k, g1, g2, nullptr, ok_out);
+    run_pairing<GTB, G1B, G2B>(k_pairing_bls, n, k, g1, g2, nullptr, ok_out);
     GG_CAPI_END
 }
 extern "C" int gg_pairing_bls12_381_host(size_t n, int k, const void* g1, const void* g2, void* gt_out) {

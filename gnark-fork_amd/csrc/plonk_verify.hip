@@ -26,7 +26,7 @@ struct Bn254 {
         fs::be_bytes<8>(from_mont(p.y).v, out + 32);
     }
     static gg::Fr hash_to_field(const uint8_t* msg, size_t len, const uint8_t* dst, size_t dst_len) {
-        return pairing::hash_to_field(msg, len, dst, dst_len);
+        return pairing::hash_to_field<gg::Fr>(msg, len, dst, dst_len);
     }
 };
 using V = Verifier<Bn254>;

@@ -47,7 +47,7 @@ struct Bls12381 {
         fs::be_bytes<12>(from_mont(p.y).v, out + 48);
     }
     static FrBls hash_to_field(const uint8_t* msg, size_t len, const uint8_t* dst, size_t dst_len) {
-        return hash_to_field_bls(msg, len, dst, dst_len);
+        return pairing::hash_to_field<FrBls>(msg, len, dst, dst_len);
     }
 };
 using VB = Verifier<Bls12381>;

@@ -39,6 +39,7 @@
 #include "common.h"
 #include "pairing.cuh"
 #include "pairing_host.h"
+#include "pairing_run.h"
 #include "prof.h"
 #include "sha256.h"
 #include "transcript.h"
@@ -86,18 +87,6 @@ GG_HD const F& at(const uint8_t* base, size_t off) {
 template <class C>
 struct Kernels;
 
-// One step over `count` lanes: a kernel launch on st, or a loop on this thread.
-template <class A>
-static void run(bool dev, hipStream_t st, void (*kern)(A), void (*body)(const A&, size_t), const A& a, size_t count,
-                unsigned block) {
-    if (!count) return;
-    if (dev) {
-        hipLaunchKernelGGL(kern, dim3(grid_for(count, block)), dim3(block), 0, st, a);
-        GG_HIP(hipGetLastError());
-    } else {
-        for (size_t i = 0; i < count; i++) body(a, i);
-    }
-}
 // a grow-only buffer on either side
 struct Buf {
     DevBuf d;

@@ -55,14 +55,18 @@ class SyntheticKey:
     """nb_inputs public inputs (without the ONE wire) and nc commitments.
     Commitment 0 commits to the public input 1 (when there is one); commitment
     j > 0 to the public input 1 and to the hash wire of commitment j - 1.
-    g1_multiples(ks) -> bytes may make the points k G1 elsewhere (the GPU)."""
+    g1_multiples(ks) -> bytes may make the points k G1 elsewhere (the GPU).
+    k_i = 0 for i in zero_k: K_i is the infinity, as for a public input that no
+    constraint uses."""
 
-    def __init__(self, nb_inputs: int, seed: int, nc: int = 0, g1_multiples=None):
+    def __init__(self, nb_inputs: int, seed: int, nc: int = 0, g1_multiples=None, zero_k=()):
         rng = random.Random(seed)
         self.rng = rng
         self.alpha, self.beta, self.gamma, self.delta, self.g, self.sigma = (rng.randrange(1, R) for _ in range(6))
         self.nb_public, self.nc = nb_inputs + 1, nc
         self.k = [rng.randrange(1, R) for _ in range(self.nb_public + nc)]
+        for i in zero_k:
+            self.k[i] = 0
         if g1_multiples is None:
             self.K = [o.g1_mul(o.G1_GEN, k) for k in self.k]
         else:
@@ -125,6 +129,39 @@ class SyntheticKey:
             beta2=o.g2_to_bytes(o.g2_mul(o.G2_GEN, self.beta)), gamma2=o.g2_to_bytes(o.g2_mul(o.G2_GEN, self.gamma)),
             delta2=o.g2_to_bytes(o.g2_mul(o.G2_GEN, self.delta)), K=b"".join(o.g1_to_bytes(p) for p in self.K),
             nb_public=self.nb_public, curve="bls12-381", **kw)
+
+
+def oracle_verify(key, proof, witness) -> bool:
+    """the pairing equation of a key without commitments, by the big-integer reference pairing"""
+    import bls_pairing_ref as br
+    assert key.nc == 0
+    g1, g2 = (lambda k: o.g1_mul(o.G1_GEN, k)), (lambda k: o.g2_mul(o.G2_GEN, k))
+    case = dict(alpha=g1(key.alpha), beta=g2(key.beta), gamma=g2(key.gamma), delta=g2(key.delta), K=key.K,
+                inputs=list(witness), ar=proof.ar, bs=proof.bs, krs=proof.krs)
+    return br.pairing_product(br.groth16_pairs(case)).is_one()
+
+
+_UNUSED = None
+
+
+def unused_input_case():
+    """A key with 2 public inputs whose K[2] is the infinity (input 2 is used by
+    no constraint) and a batch of 4: two valid proofs whose dead input has every
+    byte nonzero / is r - 1, the first proof with the dead input changed (still
+    valid) and with the live input changed.  -> (key, proofs, witnesses, statuses),
+    every status held against oracle_verify; made once per process."""
+    global _UNUSED
+    if _UNUSED is None:
+        key = SyntheticKey(2, seed=77, zero_k=(2,))
+        assert key.K[2] is o.INF and key.K[1] is not o.INF
+        dead = int.from_bytes(bytes(range(0x11, 0x31)), "big")          # 32 nonzero bytes, < r
+        wits = [[5, dead], [R - 2, R - 1], [5, dead ^ 0xFF00FF], [6, dead]]
+        p1, p2 = key.prove(wits[0]), key.prove(wits[1])
+        proofs, want = [p1, p2, p1, p1], [OK, OK, OK, PAIRING]
+        for p, w, st in zip(proofs, wits, want):
+            assert oracle_verify(key, p, w) == (st == OK)
+        _UNUSED = key, proofs, wits, want
+    return _UNUSED
 
 
 def kat_vk_data(case):

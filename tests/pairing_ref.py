@@ -110,12 +110,16 @@ def proof_bytes(proof) -> bytes:
 
 
 class SyntheticKey:
-    """A Groth16 verifying key from discrete logs: K_i = k_i G1, no circuit."""
+    """A Groth16 verifying key from discrete logs: K_i = k_i G1, no circuit.
+    k_i = 0 for i in zero_k: K_i is the infinity, as for a public input that no
+    constraint uses."""
 
-    def __init__(self, nb_inputs: int, seed: int):
+    def __init__(self, nb_inputs: int, seed: int, zero_k=()):
         rng = o.SplitMix64(seed)
         self.alpha, self.beta, self.gamma, self.delta = (rng.fr() or 1 for _ in range(4))
         self.k = [rng.fr() for _ in range(nb_inputs + 1)]
+        for i in zero_k:
+            self.k[i] = 0
         self.rng = rng
         vk = o.VerifyingKey()
         vk.g1_alpha = o.g1_mul(o.G1_GEN, self.alpha)

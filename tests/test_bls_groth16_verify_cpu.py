@@ -257,6 +257,15 @@ def test_synthetic_bsb22_key_on_the_host():
     vk.close()
 
 
+def test_unused_public_input_on_the_host():
+    """K[2] at infinity: whatever the dead input is, it adds nothing to kSum"""
+    from gnark_amd import groth16
+    key, proofs, wits, want = gr.unused_input_case()
+    vk = groth16.Bls12381VerifyingKey(key.vk_data())
+    assert groth16.verify_batch([p.gproof() for p in proofs], vk, wits, host=True) == want == [OK, OK, OK, PAIRING]
+    vk.close()
+
+
 @pytest.mark.parametrize("nb_inputs", [0, 1])
 def test_synthetic_keys_without_commitments_on_the_host(nb_inputs):
     from gnark_amd import groth16

@@ -105,6 +105,15 @@ def test_synthetic_instances(nb_inputs):
     vk.close()
 
 
+def test_unused_public_input():
+    """K[2] at infinity: its table row is all infinity and adds nothing, whatever the dead input is"""
+    from gnark_amd import groth16
+    key, proofs, wits, want = gr.unused_input_case()
+    vk = groth16.Bls12381VerifyingKey(key.vk_data())
+    assert groth16.verify_batch([p.gproof() for p in proofs], vk, wits) == want == [OK, OK, OK, PAIRING]
+    vk.close()
+
+
 def test_batch_of_67_with_every_corruption():
     from gnark_amd import groth16
     key = gr.SyntheticKey(3, seed=67)

@@ -93,6 +93,23 @@ def test_synthetic_instances(nb_inputs):
     vk.close()
 
 
+def test_unused_public_input():
+    """A public input that no constraint uses: K[2] is the infinity, its table row
+    is all infinity and adds nothing, whatever the dead input is"""
+    from gnark_amd import groth16
+    key = pr.SyntheticKey(2, seed=77, zero_k=(2,))
+    assert key.vk.g1_K[2] is None and key.vk.g1_K[1] is not None
+    vk = groth16.VerifyingKey(key.vk_data())
+    dead = int.from_bytes(bytes(range(0x11, 0x31)), "big")          # 32 nonzero bytes, < r
+    wits = [[5, dead], [o.R - 2, o.R - 1], [5, dead ^ 0xFF00FF], [6, dead]]
+    p1, p2 = key.prove(wits[0]), key.prove(wits[1])
+    proofs, want = [p1, p2, p1, p1], [OK, OK, OK, PAIRING]
+    assert groth16.verify_batch([_gproof(p) for p in proofs], vk, wits) == want
+    for p, w, st in zip(proofs, wits, want):
+        assert o.verify(p, key.vk, w) == (st == OK)
+    vk.close()
+
+
 def test_batch_with_every_corruption():
     from gnark_amd import groth16
     key = pr.SyntheticKey(3, seed=67)

@@ -20,7 +20,7 @@ the first one that fails:
              and one corrupted proof per batch must be the only failure;
   oracle     oracle/bn254_oracle.py:verify for one proof on this CPU, the only
              baseline the project has;
-  resources  the code-object figures of pairing.hip's kernels (VGPRs, scratch,
+  resources  the code-object figures of groth16_verify.hip's kernels (VGPRs, scratch,
              LDS, waves per SIMD) from the compiler's resource remarks; needs
              no GPU (--step resources --json FILE writes them, --resources-json
              FILE reuses them)."""
@@ -177,7 +177,7 @@ def step_oracle(nb_public):
     return dict(step="oracle", nb_public=nb_public, seconds=min(t))
 
 
-def step_resources(source="pairing.hip"):
+def step_resources(source="groth16_verify.hip"):
     src = os.path.join(ROOT, "gnark-fork_amd", "csrc", source)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     cmd = [hipcc, "-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-munsafe-fp-atomics",
