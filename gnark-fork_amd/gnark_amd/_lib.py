@@ -33,7 +33,9 @@ GG_SETUP_CK_BASIS, GG_SETUP_CK_BASIS_SIGMA = 0x100, 0x200
  GG_PLONK_SETUP_S2, GG_PLONK_SETUP_S3, GG_PLONK_SETUP_PERM, GG_PLONK_SETUP_LAGRANGE) = range(10)
 GG_PLONK_SETUP_QCP = 0x100
 GG_VERIFY_OK, GG_VERIFY_SUBGROUP, GG_VERIFY_PEDERSEN, GG_VERIFY_PAIRING = 0, 1, 2, 3
-GG_POINT_OK, GG_POINT_NOT_ON_CURVE, GG_POINT_NOT_IN_SUBGROUP = 0, 1, 2
+GG_POINT_OK, GG_POINT_NOT_ON_CURVE, GG_POINT_NOT_IN_SUBGROUP, GG_POINT_BAD_ENCODING = 0, 1, 2, 3
+GG_ENC_COMPRESSED, GG_ENC_RAW = 0, 1
+GG_DEC_NO_SUBGROUP_CHECK = 1
 GG_GT_BYTES = 384
 GG_GT_BYTES_BLS12_381 = 576
 GG_VERIFY_MAX_K = 1024
@@ -267,6 +269,13 @@ def _load():
         "gg_plonk_verify_batch_bls12_381_host": ([P, S, P, P, HASH_FN, P, HASH_FN, P, P], I),
         "gg_kzg_verify_bls12_381": ([S, P, P, P, P, P, P, P], I),
         "gg_kzg_verify_bls12_381_host": ([S, P, P, P, P, P, P, P], I),
+        "gg_point_encoded_size": ([I, I], S),
+        "gg_points_decode": ([I, I, I, S, P, I, P, I, P], I),
+        "gg_points_decode_host": ([I, I, I, S, P, P, P], I),
+        "gg_points_encode": ([I, I, S, P, I, P], I),
+        "gg_points_encode_host": ([I, I, S, P, P], I),
+        "gg_fp_sqrt": ([I, I, S, P, P, P], I),
+        "gg_fp_sqrt_host": ([I, I, S, P, P, P], I),
         "gg_profile_enable": ([I], I),
         "gg_profile_get": ([ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),
                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)], I),
@@ -350,6 +359,8 @@ EXPORTED = [
     "gg_g2_check_endo_bls12_381",
     "gg_plonk_vk_create_bls12_381", "gg_plonk_vk_destroy_bls12_381", "gg_plonk_verify_batch_bls12_381",
     "gg_plonk_verify_batch_bls12_381_host", "gg_kzg_verify_bls12_381", "gg_kzg_verify_bls12_381_host",
+    "gg_point_encoded_size", "gg_points_decode", "gg_points_decode_host", "gg_points_encode",
+    "gg_points_encode_host", "gg_fp_sqrt", "gg_fp_sqrt_host",
 ]
 
 

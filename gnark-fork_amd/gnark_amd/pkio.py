@@ -21,6 +21,16 @@ X.A1|X.A0|Y.A1|Y.A0; (0, 0) is infinity.  Compressed (WriteTo) = X only with the
 top two bits of the first byte as flags: 0b10 y is the smaller root, 0b11 the
 larger (E2: compare A1, then A0 if A1 = 0), 0b01 infinity.
 
+codec="python" (the default of every function here) is the BN254 codec below,
+point by point in big integers.  codec="host" / "gpu" hand whole point arrays
+to the library's codec (gnark_amd.codec: csrc/point_codec_impl.cuh, on the
+calling thread or on the GPU) for BN254 and BLS12-381 (48-byte coordinates,
+the Zcash 3-bit flags), with the curve and subgroup checks gnark's ReadFrom
+makes; unsafe=True is UnsafeReadFrom.  On the same path: the verifying key
+(read_verifying_key / write_verifying_key, marshal.go:96-230) and the proof
+(read_proof / write_proof, marshal.go:41-91).  PlonK keys and the KZG SRS are
+not covered.
+
 Parity: the reference holds no serialized key, so the byte format is "parity
 unpinned" beyond the round trips in tests/test_pkio.py; the point encoding
 rules are those pinned for BLS12-381 by bellman_test.go in test_oracle_bls.
@@ -187,11 +197,16 @@ def _g2_decode(buf: bytes, off: int, raw: bool) -> Tuple[bytes, int]:
 
 # ------------------------------------------------------------- key codec
 def write_proving_key(data, raw: bool = True, commitment_keys: Optional[List[Tuple[bytes, bytes]]] = None,
-                      out: Optional[BinaryIO] = None) -> bytes:
+                      out: Optional[BinaryIO] = None, curve: Optional[str] = None, codec: str = "python") -> bytes:
     """ProvingKey.WriteRawTo (raw=True) / WriteTo (marshal.go:246-307) of a
-    `groth16.ProvingKeyData` (BN254).  commitment_keys: (basis, basis_exp_sigma)
-    G1 arrays (gnark layout) of the pedersen keys, default none."""
-    if data.curve != "bn254":
+    `groth16.ProvingKeyData`.  commitment_keys: (basis, basis_exp_sigma)
+    G1 arrays (gnark layout) of the pedersen keys, default none.
+    codec="python" (BN254 only) encodes point by point in Python; "host" and
+    "gpu" hand every point array to the library's codec in one call
+    (codec.encode_points), for the key's curve (curve, default data.curve)."""
+    if codec != "python":
+        return _write_proving_key_lib(data, raw, commitment_keys, out, _Points(curve or data.curve, codec))
+    if data.curve != "bn254" or curve not in (None, "bn254"):
         raise ValueError("pk codec: BN254 only")
     n = 1 << data.log_n
     omega = fr.fr_unmont(data.domain_generator) if data.domain_generator else fr.domain_generator(data.log_n)
@@ -235,13 +250,22 @@ def write_proving_key(data, raw: bool = True, commitment_keys: Optional[List[Tup
     return b
 
 
-def read_proving_key(src: Union[bytes, BinaryIO], nb_public: int, k_wire_index=None):
-    """ProvingKey.ReadFrom (marshal.go:309-374) into a `groth16.ProvingKeyData`
-    (BN254); raw or compressed points, detected per point from the flag bits.
+def read_proving_key(src: Union[bytes, BinaryIO], nb_public: int, k_wire_index=None, curve: str = "bn254",
+                     codec: str = "python", unsafe: bool = False):
+    """ProvingKey.ReadFrom (marshal.go:309-374) into a `groth16.ProvingKeyData`;
+    raw or compressed points, detected from the flag bits of the first point.
     nb_public comes from the R1CS (it is not part of the key).  Returns
-    (ProvingKeyData, commitment_keys)."""
+    (ProvingKeyData, commitment_keys).
+    codec="python" (BN254 only) decodes point by point in Python, with no
+    subgroup test; "host" and "gpu" hand every point array to the library's
+    codec in one call (codec.decode_points: square roots, curve and subgroup
+    checks per point).  unsafe=True is UnsafeReadFrom (no subgroup checks)."""
     from .groth16 import ProvingKeyData
     buf = src if isinstance(src, (bytes, bytearray)) else src.read()
+    if codec != "python":
+        return _read_proving_key_lib(bytes(buf), nb_public, k_wire_index, _Points(curve, codec, unsafe))
+    if curve != "bn254":
+        raise ValueError("pk codec: codec='python' is BN254 only (use codec='host' or 'gpu')")
     if len(buf) < _DOMAIN_BYTES:
         raise ValueError("pk: truncated domain")
     n = struct.unpack(">Q", buf[:8])[0]
@@ -307,3 +331,272 @@ def read_proving_key(src: Union[bytes, BinaryIO], nb_public: int, k_wire_index=N
         g2_B=g2B, beta2=beta2, delta2=delta2, infinity_A=infA, infinity_B=infB, nb_public=nb_public,
         domain_generator=fr.fr_mont(omega), domain_mul_gen=fr.fr_mont(gen), k_wire_index=k_wire_index)
     return data, cks
+
+
+# ------------------------------------------------------------- library codecs, both curves
+# slices of at most this many points, and single points, follow each point's
+# own flag (bellman_test.go:100-101 appends a raw all-zero CommitmentPok to a
+# compressed proof); a longer slice has one encoding, read from its first point
+_SHORT = 4
+_CURVE = {  # fr modulus, fr to / from Montgomery, domain generator, multiplicative generator, (G1, G2) bytes
+    "bn254": (R, fr.fr_mont, fr.fr_unmont, fr.domain_generator, fr.FR_MULTIPLICATIVE_GEN, (64, 128)),
+    "bls12-381": (fr.BLS_R, fr.bls_fr_mont, fr.bls_fr_unmont, fr.bls_domain_generator,
+                  fr.BLS_FR_MULTIPLICATIVE_GEN, (96, 192)),
+}
+
+
+class _Points:
+    """The point codec of one call: curve, codec ("python" on BN254, or the
+    library's "host" / "gpu" entry points), and whether decoding skips the
+    subgroup checks."""
+
+    def __init__(self, curve: str, codec: str, unsafe: bool = False):
+        if curve not in _CURVE:
+            raise ValueError(f"pk codec: curve must be 'bn254' or 'bls12-381', got {curve!r}")
+        if codec not in ("python", "host", "gpu"):
+            raise ValueError(f"pk codec: codec must be 'python', 'host' or 'gpu', got {codec!r}")
+        if codec == "python" and curve != "bn254":
+            raise ValueError("pk codec: codec='python' is BN254 only (use codec='host' or 'gpu')")
+        self.curve, self.codec, self.unsafe = curve, codec, unsafe
+        self.mod, self.mont, self.unmont, self.domain_gen, self.mul_gen, self.sizes = _CURVE[curve]
+
+    def size(self, g: int) -> int:
+        return self.sizes[g - 1]
+
+    def _group(self, g: int) -> int:
+        from . import codec as C
+        return C.GROUPS[(self.curve, g)]
+
+    def is_raw(self, first: int) -> bool:
+        return (first >> 6) == 0 if self.curve == "bn254" else (first >> 5) in (0, 2)
+
+    def encode(self, pts: bytes, g: int, raw: bool) -> bytes:
+        if not pts:
+            return b""
+        if self.codec == "python":
+            sz, f = self.size(g), (_g1_encode if g == 1 else _g2_encode)
+            return b"".join(f(pts[i:i + sz], raw) for i in range(0, len(pts), sz))
+        from . import codec as C
+        return C.encode_points(pts, self._group(g), raw=raw, host=self.codec == "host")
+
+    def _decode_run(self, buf: bytes, off: int, g: int, n: int, raw: bool, what: str) -> Tuple[bytes, int]:
+        esz = self.size(g) // (1 if raw else 2)
+        if off + n * esz > len(buf):
+            raise ValueError(f"{what}: truncated")
+        if self.codec == "python":
+            f, out = (_g1_decode if g == 1 else _g2_decode), []
+            for _ in range(n):
+                p_, off = f(buf, off, raw)
+                out.append(p_)
+            return b"".join(out), off
+        from . import codec as C
+        try:
+            pts = C.decode_points(buf[off:off + n * esz], self._group(g), n, raw=raw,
+                                  subgroup_check=not self.unsafe, host=self.codec == "host")
+        except ValueError as e:
+            raise ValueError(f"{what}: {e}") from None
+        return pts, off + n * esz
+
+    def decode(self, buf: bytes, off: int, g: int, n: int, what: str) -> Tuple[bytes, int]:
+        """n points of group g (1 or 2) at buf[off:] -> (affine Montgomery bytes, new offset)"""
+        if n == 0:
+            return b"", off
+        if off >= len(buf):
+            raise ValueError(f"{what}: truncated")
+        if n > _SHORT:
+            return self._decode_run(buf, off, g, n, self.is_raw(buf[off]), what)
+        out = []
+        for i in range(n):
+            if off >= len(buf):
+                raise ValueError(f"{what}: truncated")
+            p_, off = self._decode_run(buf, off, g, 1, self.is_raw(buf[off]), what if n == 1 else f"{what}[{i}]")
+            out.append(p_)
+        return b"".join(out), off
+
+
+class _Cursor:
+    def __init__(self, buf: bytes, pts: _Points, name: str):
+        self.buf, self.off, self.pts, self.name = buf, 0, pts, name
+
+    def take(self, k: int) -> bytes:
+        if self.off + k > len(self.buf):
+            raise ValueError(f"{self.name}: truncated")
+        self.off += k
+        return self.buf[self.off - k:self.off]
+
+    def u32(self) -> int:
+        return struct.unpack(">I", self.take(4))[0]
+
+    def u64(self) -> int:
+        return struct.unpack(">Q", self.take(8))[0]
+
+    def point(self, g: int, what: str) -> bytes:
+        p_, self.off = self.pts.decode(self.buf, self.off, g, 1, f"{self.name}: {what}")
+        return p_
+
+    def vec(self, g: int, what: str) -> bytes:
+        n = self.u32()
+        p_, self.off = self.pts.decode(self.buf, self.off, g, n, f"{self.name}: {what}")
+        return p_
+
+
+def _write_proving_key_lib(data, raw, commitment_keys, out, pts: _Points) -> bytes:
+    if data.curve != pts.curve:
+        raise ValueError(f"pk codec: a {data.curve!r} key, curve={pts.curve!r}")
+    n = 1 << data.log_n
+    mod = pts.mod
+    omega = pts.unmont(data.domain_generator) if data.domain_generator else pts.domain_gen(data.log_n)
+    g = pts.unmont(data.domain_mul_gen) if data.domain_mul_gen else pts.mul_gen
+    w = io.BytesIO()
+    w.write(struct.pack(">Q", n))
+    for v in (pow(n, -1, mod), omega, pow(omega, -1, mod), g, pow(g, -1, mod)):
+        w.write(_be(v))
+
+    def vec(b, gidx):
+        w.write(struct.pack(">I", len(b) // pts.size(gidx)))
+        w.write(pts.encode(bytes(b), gidx, raw))
+
+    w.write(pts.encode(bytes(data.alpha1) + bytes(data.beta1) + bytes(data.delta1), 1, raw))
+    for v in (data.g1_A, data.g1_B, data.g1_Z, data.g1_K):
+        vec(v, 1)
+    w.write(pts.encode(bytes(data.beta2) + bytes(data.delta2), 2, raw))
+    vec(data.g2_B, 2)
+    infA, infB = bytes(data.infinity_A), bytes(data.infinity_B)
+    w.write(struct.pack(">QQQ", len(infA), sum(1 for c in infA if c), sum(1 for c in infB if c)))
+    w.write(bytes(1 if c else 0 for c in infA))
+    w.write(bytes(1 if c else 0 for c in infB))
+    cks = commitment_keys or []
+    w.write(struct.pack(">I", len(cks)))
+    for basis, sigma in cks:
+        vec(basis, 1)
+        vec(sigma, 1)
+    b = w.getvalue()
+    if out is not None:
+        out.write(b)
+    return b
+
+
+def _read_proving_key_lib(buf: bytes, nb_public: int, k_wire_index, pts: _Points):
+    from .groth16 import ProvingKeyData
+    c = _Cursor(buf, pts, "pk")
+    if len(buf) < _DOMAIN_BYTES:
+        raise ValueError("pk: truncated domain")
+    n = c.u64()
+    if n == 0 or n & (n - 1):
+        raise ValueError("pk: domain cardinality is not a power of two")
+    vals = [int.from_bytes(c.take(32), "big") for _ in range(5)]
+    if any(v >= pts.mod for v in vals):
+        raise ValueError("pk: domain element not reduced")
+    _, omega, _, gen, _ = vals
+    alpha1, beta1, delta1 = c.point(1, "G1.Alpha"), c.point(1, "G1.Beta"), c.point(1, "G1.Delta")
+    gA, gB, gZ, gK = c.vec(1, "G1.A"), c.vec(1, "G1.B"), c.vec(1, "G1.Z"), c.vec(1, "G1.K")
+    beta2, delta2 = c.point(2, "G2.Beta"), c.point(2, "G2.Delta")
+    g2B = c.vec(2, "G2.B")
+    nw, ninfA, ninfB = c.u64(), c.u64(), c.u64()
+    infA, infB = c.take(nw), c.take(nw)
+    if any(x > 1 for x in infA + infB):
+        raise ValueError("pk: infinity flags must be 0/1")
+    if sum(infA) != ninfA or sum(infB) != ninfB:
+        raise ValueError("pk: NbInfinityA/B disagree with the flags")
+    g1b, g2b = pts.sizes
+    if len(gA) // g1b != nw - ninfA or len(gB) // g1b != nw - ninfB or len(g2B) // g2b != nw - ninfB:
+        raise ValueError("pk: point counts disagree with the infinity flags")
+    cks = []
+    for j in range(c.u32()):
+        cks.append((c.vec(1, f"CommitmentKeys[{j}].Basis"), c.vec(1, f"CommitmentKeys[{j}].BasisExpSigma")))
+    data = ProvingKeyData(
+        log_n=n.bit_length() - 1, g1_A=gA, g1_B=gB, g1_Z=gZ, g1_K=gK, alpha1=alpha1, beta1=beta1, delta1=delta1,
+        g2_B=g2B, beta2=beta2, delta2=delta2, infinity_A=infA, infinity_B=infB, nb_public=nb_public,
+        domain_generator=pts.mont(omega), domain_mul_gen=pts.mont(gen), k_wire_index=k_wire_index, curve=pts.curve)
+    return data, cks
+
+
+# ------------------------------------------------------------- verifying key and proof
+def write_verifying_key(data, raw: bool = False, out: Optional[BinaryIO] = None, codec: str = "python") -> bytes:
+    """VerifyingKey.WriteTo (raw=True: WriteRawTo) of a `groth16.VerifyingKeyData`
+    (marshal.go:96-162): alpha1, beta1, beta2, gamma2, delta1, delta2, u32 length + K,
+    PublicAndCommitmentCommitted as a slice of uint64 slices, then the Pedersen
+    verifying key (G, GRootSigmaNeg; the infinity twice for a key without
+    commitments)."""
+    pts = _Points(data.curve, codec)
+    g1b, g2b = pts.sizes
+    w = io.BytesIO()
+    w.write(pts.encode(bytes(data.alpha1) + bytes(data.beta1), 1, raw))
+    w.write(pts.encode(bytes(data.beta2) + bytes(data.gamma2), 2, raw))
+    w.write(pts.encode(bytes(data.delta1), 1, raw))
+    w.write(pts.encode(bytes(data.delta2), 2, raw))
+    w.write(struct.pack(">I", len(data.K) // g1b))
+    w.write(pts.encode(bytes(data.K), 1, raw))
+    committed = [list(c_) for c_ in data.public_and_commitment_committed]
+    w.write(struct.pack(">I", len(committed)))
+    for c_ in committed:
+        w.write(struct.pack(">I", len(c_)))
+        w.write(b"".join(struct.pack(">Q", int(i)) for i in c_))
+    ped = (bytes(data.commitment_key_g or bytes(g2b)) + bytes(data.commitment_key_g_root_sigma_neg or bytes(g2b)))
+    w.write(pts.encode(ped, 2, raw))
+    b = w.getvalue()
+    if out is not None:
+        out.write(b)
+    return b
+
+
+def read_verifying_key(src: Union[bytes, BinaryIO], curve: str = "bn254", codec: str = "python",
+                       unsafe: bool = False):
+    """VerifyingKey.ReadFrom (marshal.go:169-230; unsafe=True: UnsafeReadFrom)
+    into a `groth16.VerifyingKeyData`; nb_public = len(K) - the number of
+    commitments.  The Pedersen key of a key without commitments (the infinity
+    twice) reads as None."""
+    from .groth16 import VerifyingKeyData
+    buf = bytes(src if isinstance(src, (bytes, bytearray)) else src.read())
+    pts = _Points(curve, codec, unsafe)
+    c = _Cursor(buf, pts, "vk")
+    alpha1, beta1 = c.point(1, "G1.Alpha"), c.point(1, "G1.Beta")
+    beta2, gamma2 = c.point(2, "G2.Beta"), c.point(2, "G2.Gamma")
+    delta1, delta2 = c.point(1, "G1.Delta"), c.point(2, "G2.Delta")
+    K = c.vec(1, "G1.K")
+    committed = []
+    for _ in range(c.u32()):
+        committed.append([c.u64() for _ in range(c.u32())])
+    g, gs = c.point(2, "CommitmentKey.G"), c.point(2, "CommitmentKey.GRootSigmaNeg")
+    nK = len(K) // pts.size(1)
+    if len(committed) >= max(nK, 1):
+        raise ValueError(f"vk: {len(committed)} commitments but only {nK} points in K")
+    if not committed and not any(g) and not any(gs):
+        g = gs = None
+    return VerifyingKeyData(alpha1=alpha1, beta1=beta1, delta1=delta1, beta2=beta2, gamma2=gamma2, delta2=delta2,
+                            K=K, nb_public=nK - len(committed), commitment_key_g=g,
+                            commitment_key_g_root_sigma_neg=gs, public_and_commitment_committed=committed or (),
+                            curve=curve)
+
+
+def write_proof(proof, raw: bool = False, out: Optional[BinaryIO] = None, curve: str = "bn254",
+                codec: str = "python") -> bytes:
+    """Proof.WriteTo (raw=True: WriteRawTo) of a `groth16.Proof` (marshal.go:41-66):
+    Ar, Bs, Krs, u32 length + Commitments, CommitmentPok."""
+    pts = _Points(curve, codec)
+    g1b = pts.size(1)
+    cm = [bytes(x) for x in proof.Commitments]
+    pok = bytes(proof.CommitmentPok)
+    if not cm and len(pok) != g1b and not any(pok):
+        pok = bytes(g1b)  # the dataclass's default PoK is BN254's infinity
+    b = (pts.encode(bytes(proof.Ar), 1, raw) + pts.encode(bytes(proof.Bs), 2, raw)
+         + pts.encode(bytes(proof.Krs), 1, raw) + struct.pack(">I", len(cm)) + pts.encode(b"".join(cm), 1, raw)
+         + pts.encode(pok, 1, raw))
+    if out is not None:
+        out.write(b)
+    return b
+
+
+def read_proof(src: Union[bytes, BinaryIO], curve: str = "bn254", codec: str = "python", unsafe: bool = False):
+    """Proof.ReadFrom (marshal.go:70-91) into a `groth16.Proof`; every point
+    follows its own flag, so a compressed proof may end in a raw CommitmentPok."""
+    from .groth16 import Proof
+    buf = bytes(src if isinstance(src, (bytes, bytearray)) else src.read())
+    pts = _Points(curve, codec, unsafe)
+    c = _Cursor(buf, pts, "proof")
+    ar, bs, krs = c.point(1, "Ar"), c.point(2, "Bs"), c.point(1, "Krs")
+    cm = c.vec(1, "Commitments")
+    pok = c.point(1, "CommitmentPok")
+    g1b = pts.size(1)
+    return Proof(Ar=ar, Bs=bs, Krs=krs, Commitments=tuple(cm[i:i + g1b] for i in range(0, len(cm), g1b)),
+                 CommitmentPok=pok)

@@ -1368,6 +1368,62 @@ int gg_kzg_verify_bls12_381(size_t n, const void *kzg_g1, const void *kzg_g2, co
 int gg_kzg_verify_bls12_381_host(size_t n, const void *kzg_g1, const void *kzg_g2, const void *digests,
                                  const void *quotients, const void *points, const void *values, uint8_t *ok_out);
 
+/* ------------------------------------------------------------ point codec
+ * gnark-crypto's point Decoder / Encoder (curve.NewDecoder / NewEncoder, what
+ * every WriteTo / ReadFrom of a key or a proof goes through) for batches of
+ * points of one group: GG_G1, GG_G2 (BN254), GG_BLS12_381_G1, GG_BLS12_381_G2.
+ *
+ * Points side: the library's affine Montgomery little-endian layout, the
+ * infinity all zero (64 / 128 / 96 / 192 B per point).  Bytes side: big-endian
+ * canonical coordinates, G2 as X.A1 | X.A0 | Y.A1 | Y.A0, flags in the top bits
+ * of the first byte; gg_point_encoded_size bytes per point (GG_ENC_COMPRESSED:
+ * 32 / 64 / 48 / 96, GG_ENC_RAW twice that; 0 for an unknown group or enc).
+ *   BN254, 2 bits:      00 raw, 01 compressed infinity, 10 / 11 compressed
+ *                       with y the smaller / larger root; raw infinity all zero
+ *   BLS12-381, 3 bits:  000 raw, 010 raw infinity, 100 / 101 compressed smaller
+ *                       / larger, 110 compressed infinity; 001, 011, 111 invalid
+ * "larger" is LexicographicallyLargest: y > (p - 1) / 2 on the canonical value;
+ * in Fp2, of A1, or of A0 when A1 = 0.  An all-zero raw point decodes to the
+ * infinity on both curves; the bytes after an infinity flag are not looked at.
+ *
+ * Decoding a compressed point takes the square root of x^3 + b (checked by
+ * squaring) and picks the root the flag names; a raw point is checked against
+ * the curve equation.  Then the subgroup test: none on BN254 G1, the
+ * multiplication by r of gg_g2_check_bn254 on BN254 G2, the endomorphism tests
+ * of gg_g1_check_endo_bls12_381 / gg_g2_check_endo_bls12_381 on BLS12-381.
+ * flags = GG_DEC_NO_SUBGROUP_CHECK (gnark's UnsafeReadFrom) skips the subgroup
+ * test and the curve test of raw points; a compressed x with no y still fails.
+ *
+ * status_out[i] (uint8, host memory): GG_POINT_OK, GG_POINT_NOT_ON_CURVE (a raw
+ * point off the curve or an x with no y), GG_POINT_NOT_IN_SUBGROUP, or
+ * GG_POINT_BAD_ENCODING: an invalid flag, a flag that disagrees with enc, or a
+ * coordinate >= p.  Precedence: BAD_ENCODING, NOT_ON_CURVE, NOT_IN_SUBGROUP.  A
+ * point that is not OK is written as the infinity.  The call returns GG_OK
+ * whenever it ran.  bytes / points_out / points are device memory when their
+ * *_on_device argument is nonzero, else host memory; bytes_out is host memory.
+ * A launch handles at most 2^20 points and the host walks the chunks
+ * (GG_CODEC_CHUNK), each ended by a bounded wait.  The _host entry points run
+ * the same per-point code on the calling thread, with no device call.
+ *
+ * gg_fp_sqrt: out[i] = the root of in[i] exactly as the decoder computes it and
+ * ok_out[i] = 1 iff its square is in[i]; degree 1: Fp elements, degree 2: Fp2
+ * {A0, A1}, Montgomery form, of curve GG_CURVE_BN254 (32 B limbs) or
+ * GG_CURVE_BLS12_381 (48 B).  Pointers: host or device (found by
+ * hipPointerGetAttributes); the _host variant takes host pointers. */
+#define GG_POINT_BAD_ENCODING 3
+#define GG_ENC_COMPRESSED 0
+#define GG_ENC_RAW 1
+#define GG_DEC_NO_SUBGROUP_CHECK 1
+size_t gg_point_encoded_size(int group, int enc);
+int gg_points_decode(int group, int enc, int flags, size_t n, const void *bytes, int bytes_on_device,
+                     void *points_out, int out_on_device, uint8_t *status_out);
+int gg_points_decode_host(int group, int enc, int flags, size_t n, const void *bytes, void *points_out,
+                          uint8_t *status_out);
+int gg_points_encode(int group, int enc, size_t n, const void *points, int points_on_device, void *bytes_out);
+int gg_points_encode_host(int group, int enc, size_t n, const void *points, void *bytes_out);
+int gg_fp_sqrt(int curve, int degree, size_t n, const void *in_mont, void *out_mont, uint8_t *ok_out);
+int gg_fp_sqrt_host(int curve, int degree, size_t n, const void *in_mont, void *out_mont, uint8_t *ok_out);
+
 /* ------------------------------------------------------------ profiling
  * Kernel-level timing with HIP events recorded on the stream each kernel is
  * launched on (bench.py uses it for the roofline of the dominant kernel).
